@@ -1,7 +1,14 @@
 #!/usr/bin/env python
 """Headline benchmark: TransFuser training samples/s (one RGB+LiDAR pair = one sample), bs=10/GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full`` adds everything else the benchmark knows (in-step
+MFMA / HBM rooflines, the f32x3 line, BASELINE configs[2..4], the multi-GPU path on one GPU, the CPU baseline: several minutes).
+``--dump-outputs DIR`` writes what the last timed step returned (the total loss and the 11 detailed losses) as DIR/<name>.npy; model,
+batch and dropout seeds are fixed, so two builds can be compared output for output - up to the step's own run-to-run noise: several backward
+reductions end in fp32 atomics and AdamW amplifies their last-bit differences (two runs of one build: ~1e-4 relative after 25 steps,
+growing with the step count; tests/test_model_gpu.py::test_engine_graph_replay_matches_eager bounds it).
 
 N > 1 works both ways: launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (one rank per GPU, the
 driver's command) or from a bare shell - without a torchrun environment bench.py spawns its N ranks itself (127.0.0.1 rendezvous),
@@ -80,8 +87,13 @@ def parse_args():
                          "(<= 8 = Engine.DEFAULT_CUTS + 1), every segment's gradient range all-reduced bucket by bucket on the side stream between the replays, the "
                          "reducer told it has 2 ranks (so the 1 / world scale runs), AdamW waiting for the side stream: what the per-GPU step costs when it is not ONE graph")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra measurements the default f32 line embeds (N=1 only): f32x3, BASELINE configs[2..4], the multi-GPU path on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the in-step MFMA / HBM roofline censuses and (N=1) the f32x3 line, BASELINE configs[2..4], the multi-GPU path on one GPU "
+                         "and the CPU baseline, all embedded in the JSON line (minutes; a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the last timed train_step returned (total loss -> loss.npy, each detailed loss -> <its name>.npy, float32) into DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the extra measurements the f32 line embeds (N=1 only): f32x3, BASELINE configs[2..4], the multi-GPU path on one GPU")
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--emulate-cpu", action="store_true",
                     help="DRY RUN of the multi-rank plumbing on a machine without GPUs (tests/test_distributed_cpu.py): tiny trunks, the HIP kernels "
@@ -429,7 +441,7 @@ def alt_precision_line(args, log):
     an exact 3-way bf16 split on the bf16 MFMA), measured by a child process right after the headline so both lines come from one box.  The
     headline stays the exact-fp32-MFMA line; this object is additional evidence (tests: test_f32x3_split_mode*, error vs fp64 <= the fp32 path's)."""
     torch_free()
-    cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "f32x3", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--dtype", "f32x3", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline",
            "--backbone", args.backbone, "--dropout", str(args.dropout)] + (["--batch", str(args.batch)] if args.batch else []) + \
           (["--height", str(args.height)] if args.height else []) + (["--no-graph"] if args.no_graph else [])
     try:
@@ -445,7 +457,7 @@ def alt_precision_line(args, log):
 def child_line(extra, log, what, timeout=600):
     """One more bench line from a CHILD process on the same box (own process: own RCCL group / precision / plans; never kills the headline)."""
     torch_free()
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-alt"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-alt"] + extra
     try:
         out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=timeout).stdout.decode().strip().splitlines()
         d = json.loads(out[-1])
@@ -481,6 +493,15 @@ def multi_gpu_path_line(args, single_ms, log):
             "backward_pieces": d["check"]["backward_pieces"], "allreduce_exposed_ms": d["check"]["allreduce_exposed_ms"][0], "grad_dtype": d["check"]["grad_dtype"],
             "note": "world-size-1 RCCL group, the reducer told it has 2 ranks: every segment's arena range is all-reduced in 64 MB buckets on the side stream between the graph "
                     "replays (identity on one rank, but every launch, event and wait of the 8-GPU step is there); 1 / world rides on AdamW's gradient scale, so THIS run's updates use half the gradient (a timing run: the loss curve of the line is not the single-GPU one)"}
+
+
+def dump_outputs(path, tot, det):
+    """--dump-outputs: the return value of the last timed Engine.train_step - (total loss, dict of the detailed losses) - one float32 .npy per scalar."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), tot.detach().float().cpu().numpy())
+    for k, v in det.items():
+        np.save(os.path.join(path, "%s.npy" % k), v.detach().float().cpu().numpy())
 
 
 def torch_free():
@@ -636,6 +657,9 @@ def main():
         dt = float(t)
     loss = float(tot)
     log("timed region done: %.2f ms/step" % (dt / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tot, det)
+        log("outputs of the last timed step written to %s" % args.dump_outputs)
     assert loss == loss, "NaN loss"
     check = None
     if args.check or (world > 1 and not args.no_check):      # outside the timed region; default ON for every multi-GPU run (first-contact hardening: no > 1-GPU lease has
@@ -648,9 +672,11 @@ def main():
                 raise
             check = {"replicas_equal": False, "error": str(e)[:400]}
             log("replica check FAILED (reported, not fatal without --check): %s" % str(e)[:200])
-    roof = dominant_kernel_roofline(eng, batch, dev, log, peak, headline_workload=(backbone == "transFuser" and B == 10 and H == 256))      # every rank runs the census step (it contains the collectives); rank 0 reports
-    roof_hbm = {"skipped": "single-rank runs only: the census is one more training step with collectives inside a try / except - a rank that failed in it would leave the others in all_reduce"}
-    if world == 1 and not args.force_pieces:
+    roof, roof_hbm = {}, None      # a plain run: only the step-level figures that follow from the headline itself
+    if args.full:
+        roof = dominant_kernel_roofline(eng, batch, dev, log, peak, headline_workload=(backbone == "transFuser" and B == 10 and H == 256))      # every rank runs the census step (it contains the collectives); rank 0 reports
+        roof_hbm = {"skipped": "single-rank runs only: the census is one more training step with collectives inside a try / except - a rank that failed in it would leave the others in all_reduce"}
+    if args.full and world == 1 and not args.force_pieces:
         try:
             roof_hbm = hbm_rooflines(eng, batch, dev, log)               # the same for the bandwidth-bound kernels north_star names
         except Exception as e:   # additional evidence only: never kill the headline line
@@ -685,13 +711,14 @@ def main():
             roof["step_frac"] = round(step_tf / peak, 4)
             roof["step_frac_of_fp16_mfma_peak"] = round(step_tf / PEAK_BF16_MFMA_TF, 4)      # north_star quotes the 16-bit MFMA roofline (2.5 PFLOP/s dense) for every line
         res["roofline"] = roof
-        res["roofline_hbm"] = roof_hbm
-        if world == 1 and args.dtype == "f32" and not args.no_alt:
+        if roof_hbm is not None:
+            res["roofline_hbm"] = roof_hbm
+        if args.full and world == 1 and args.dtype == "f32" and not args.no_alt:
             res["f32x3"] = alt_precision_line(args, log)
             if backbone == "transFuser" and not args.batch and not args.height and not args.no_graph:      # the headline invocation: the other BASELINE configs + the N > 1 path
                 res["configs"] = baseline_config_lines(args, log)
                 res["multi_gpu_path_on_one_gpu"] = multi_gpu_path_line(args, ms, log)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(make_cfg, backbone, H, W)
         print(json.dumps(res), flush=True)
     if world > 1:
