@@ -28,6 +28,13 @@ const char* tf_build_id(void);
 /* Stream-K GEMM launches issued by this process so far (diagnostics / tests: a pinned stream-K plan silently falls back to the data-parallel
  * launch when the call carries no scratch or the tile count divides evenly). */
 long tf_streamk_launches(void);
+/* 16-byte epilogue of the register-staged GEMM engine (transposed accumulator; the reference's cuBLAS / cuDNN epilogues behind
+ * transfuser.py:380,442,539-549 have no such knob).  TF_GEMM_EPI16=0 in the environment keeps every launch on the 4-byte epilogue.
+ * tf_gemm_epi16(0 | 1) sets the switch, tf_gemm_epi16(-1) re-reads the environment; both return the value now in force (tests).
+ * tf_gemm_epi16_launches(): launches configured with the 16-byte epilogue so far - a query, it changes no result: a call that is not
+ * eligible (alignment, N % 4, atomic mode, tiling) silently takes the 4-byte epilogue and leaves the counter alone. */
+int tf_gemm_epi16(int on);
+long tf_gemm_epi16_launches(void);
 
 /* GEMM tiling plans.  The reference turns on cudnn.benchmark (train.py:115); the equivalent here: while tf_autotune(1)
  * is on (eager warm-up, NOT during graph capture - it synchronises), the first call of every distinct

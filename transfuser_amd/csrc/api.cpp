@@ -43,6 +43,7 @@ extern "C" const char* tf_build_id(void) { return TF_BUILD_ID; }
 extern "C" int tf_version(void) { return 101; }
 extern "C" long tf_streamk_launches(void) { return tf::streamk_count(0); }
 extern "C" const char* tf_last_error(void) { return tf::g_err; }
+extern "C" long tf_gemm_epi16_launches(void) { return tf::epi16_count(0); }
 
 // ---- GEMM plan cache / autotuner switches -----------------------------------------------------------------------
 namespace tf {
@@ -64,6 +65,10 @@ void plan_store(const char* what, int M, int N, int K, int batch, int acc, const
 }
 bool autotune_enabled() { return g_autotune; }
 long streamk_count(int add) { static long n = 0; n += add; return n; }
+long epi16_count(int add) { static long n = 0; n += add; return n; }
+static int g_epi16 = -1;
+static int epi16_from_env() { const char* e = getenv("TF_GEMM_EPI16"); return (!e || atoi(e) != 0) ? 1 : 0; }
+int gemm_epi16() { if (g_epi16 < 0) g_epi16 = epi16_from_env(); return g_epi16; }
 int device_cus() {
 #ifdef TF_EMU
     return 8;                       // small on purpose: the emulated stream-K launches cut tiles on test-sized problems
@@ -83,6 +88,10 @@ bool forced_plan(GemmPlan* out) { if (g_forced.bm == 0) return false; *out = g_f
 static bool plan_tile_ok(int bm, int bn, int bk, int sk, int kind) {
     if (kind != 0) { const tf::DmaKindInfo ki = tf::dma_kind_info(kind); return kind >= 1 && kind <= tf::kDmaKinds && sk >= 1 && ki.bm == bm && ki.bn == bn && ki.bk == bk; }
     return ((bm == 128 && (bn == 32 || bn == 64 || bn == 96 || bn == 128)) || (bm == 64 && (bn == 64 || bn == 128))) && (bk == 16 || bk == 32) && sk >= 1;
+}
+extern "C" int tf_gemm_epi16(int on) {
+    if (on >= 0) tf::g_epi16 = on != 0; else tf::g_epi16 = tf::epi16_from_env();
+    return tf::g_epi16;
 }
 extern "C" int tf_force_dma(int kind, int splitk) {
     if (kind < 1 || kind > tf::kDmaKinds || splitk < 1) { tf::set_error("tf_force_dma: unknown LDS-DMA configuration %d", kind); return -1; }

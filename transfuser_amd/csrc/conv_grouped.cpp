@@ -959,7 +959,7 @@ extern "C" int tf_conv3x3_grouped_fwd_f32(const float* x, const float* w, const 
     if (prec == 2) {
         if (tw == 16) TF_LAUNCH((conv3x3_grouped_kernel<16, true>), dim3(g.G * g.nb), dim3(256), stream, x, w, bias, y, g, 0, relu, 0, 2, (float*)nullptr);
         else TF_LAUNCH((conv3x3_grouped_kernel<32, true>), dim3(g.G * g.nb), dim3(256), stream, x, w, bias, y, g, 0, relu, 0, 2, (float*)nullptr);
-    } else if (prec == 0 && f32t_on()) {        // exact fp32: the transposed-accumulator instantiation (16-byte stores)
+    } else if (prec == 0 && f32t_on() && (!bias || aligned16(bias))) {        // exact fp32: the transposed-accumulator instantiation (16-byte stores, 16-byte bias loads)
         if (tw == 16) TF_LAUNCH((conv3x3_grouped_kernel<16, false, false, true>), dim3(g.G * g.nb), dim3(256), stream, x, w, bias, y, g, 0, relu, 0, 0, (float*)nullptr);
         else TF_LAUNCH((conv3x3_grouped_kernel<32, false, false, true>), dim3(g.G * g.nb), dim3(256), stream, x, w, bias, y, g, 0, relu, 0, 0, (float*)nullptr);
     } else if (tw == 16) TF_LAUNCH((conv3x3_grouped_kernel<16, false>), dim3(g.G * g.nb), dim3(256), stream, x, w, bias, y, g, 0, relu, 0, prec, (float*)nullptr);

@@ -257,6 +257,8 @@ struct GemmEpi {
     // the contiguous (M, N) output, so the backward's tf_dropout_f32 regenerates it.  Batch 1, ldc == N.  (round 5: one launch less per residual branch)
     const uint32_t* drop_seed = nullptr; uint32_t drop_site = 0, drop_thresh = 0; float drop_scale = 1.f;
     int prec = 0;                    // 0: exact fp32 MFMA; 1: operands rounded to bf16 on the LDS->register path, bf16 MFMA, fp32 accumulate; 2: bf16x3 split (fp32-accurate, 6 bf16 MFMAs); 3: as 1 with IEEE-half operands (set by launch_cfg)
+    int trn = 0;                     // 1: TRANSPOSED accumulator (the MFMA takes the B fragment as its first operand: a lane owns 4 x 4 consecutive columns of ONE row) and the
+                                     // 16-byte epilogue gemm_epilogue_t; set by cfg_geom when epi16_eligible() holds, never by a caller (the LDS-DMA kernels keep 0)
     int packed16 = 0;                // LDS-DMA kernels, both operands K-contiguous: the operands ARE 16-bit matrices (1: bf16, 2: IEEE half) described in units of
                                      // 4 bytes (ld, cols, K = halves / 2): tiles are moved as bytes, one ds_read_b128 = one 8-deep MFMA operand (tf_gemm16_nt_f32)
 };
@@ -353,6 +355,61 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[TM][TN], const
             }
         }
     }
+}
+
+// Transposed form (GemmEpi::trn, one 32x32 tile per wave): lane holds ROW i0 + wm0 + (lane & 31); register r holds column (r & 3) + 8 (r >> 2) + 4 (lane >> 5),
+// i.e. four runs of 4 consecutive columns - 4 x 16-byte stores per lane instead of 16 x 4-byte ones (residual / mask / bias / accumulator reads
+// likewise).  Per element the same operations in the same order as gemm_epilogue.  Modes 0 / 1 only; the host guarantees N % 4 == 0 and the
+// 16-byte alignment of every row segment touched (epi16_eligible), so a 4-column group is inside the matrix or outside it as a whole.
+__device__ __forceinline__ void gemm_epilogue_t(const f32x16& acc, const GemmEpi& ep, int M, int N, int i0, int j0, int wm0, int wn0, int z) {
+    const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
+    const long cz = (long)(z / ep.inner) * ep.sc_outer + (long)(z % ep.inner) * ep.sc_inner;
+    float* C = ep.C + cz;
+    const float* res = ep.res ? ep.res + cz : nullptr;
+    const float* bias = ep.bias ? ep.bias + (long)z * ep.sbias : nullptr;
+    if (ep.prec & 0x100) return;
+    const uint32_t dseed = ep.drop_seed ? *ep.drop_seed : 0u;
+    const int i = i0 + wm0 + l31;
+    const bool iok = i < M;
+    auto emit = [&](auto mode_c, auto res_c) {
+        constexpr int MODE = decltype(mode_c)::value;
+        constexpr bool RES = decltype(res_c)::value;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int j = j0 + wn0 + 8 * g + 4 * hi;
+            if (iok && j < N) {
+                const float4 b4 = bias ? *reinterpret_cast<const float4*>(bias + j) : f4zero();
+                const float bj[4] = {b4.x, b4.y, b4.z, b4.w};
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = ep.alpha * acc[4 * g + e] + bj[e];
+                    if (ep.drop_seed) v[e] = dropout_keep(dseed, ep.drop_site, (uint32_t)((long)i * N + j + e), ep.drop_thresh) ? v[e] * ep.drop_scale : 0.f;
+                }
+                if (RES) {
+                    const float4 r4 = *reinterpret_cast<const float4*>(res + (long)i * ep.ldres + j);
+                    v[0] += r4.x; v[1] += r4.y; v[2] += r4.z; v[3] += r4.w;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = ep.relu ? fmaxf(v[e], 0.f) : v[e];
+                if (ep.mask) {
+                    const float4 m4 = *reinterpret_cast<const float4*>(ep.mask + (long)i * ep.ldmask + j);
+                    v[0] = m4.x > 0.f ? v[0] : 0.f; v[1] = m4.y > 0.f ? v[1] : 0.f; v[2] = m4.z > 0.f ? v[2] : 0.f; v[3] = m4.w > 0.f ? v[3] : 0.f;
+                }
+                float4* dst = reinterpret_cast<float4*>(C + (long)i * ep.ldc + j);
+                if (MODE == 1) {
+                    const float4 o = *dst;
+                    v[0] = o.x + v[0]; v[1] = o.y + v[1]; v[2] = o.z + v[2]; v[3] = o.w + v[3];
+                }
+                *dst = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        }
+    };
+    auto by_res = [&](auto mode_c) {
+        if (res) emit(mode_c, std::true_type()); else emit(mode_c, std::false_type());
+    };
+    if (ep.mode == 0) by_res(std::integral_constant<int, 0>());
+    else by_res(std::integral_constant<int, 1>());
 }
 
 // ---------------------------------------------------------------- kernel
@@ -563,29 +620,59 @@ __device__ __forceinline__ void gemm_tile(LA& la, LB& lb, const GemmEpi& ep, int
     const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wm0 = (wave % WAVES_M) * WM, wn0 = (wave / WAVES_M) * WN;
 
+    // TRANSPOSED accumulator (ep.trn, block-uniform, one 32x32 tile per wave only): the two LDS tiles and their wave offsets swap roles ONCE here -
+    // the MFMA's first operand is then the B fragment (column wn0 + l31), its second the A fragment (row wm0 + l31), and the accumulator holds the
+    // transpose of the wave's tile: the same k-ordered sum of the same products per element, laid out for gemm_epilogue_t.  In the TRN_OK
+    // instantiations the K loop reads its fragments through xa / xb either way: no branch and no second instantiation of the loop.  Every other
+    // instantiation (several tiles per wave, element-wise loads: some sit at their register cap) compiles the constant-offset As / Bs indexing.
+    constexpr bool TRN_OK = TM == 1 && TN == 1 && ALLVEC;
+    constexpr int LDA = BM + GEMM_PAD, LDB = BN + GEMM_PAD;
+    const bool trn = TRN_OK && ep.trn != 0;
+    const float* xa = trn ? &Bs[0][hi][wn0 + l31] : &As[0][hi][wm0 + l31];
+    const float* xb = trn ? &As[0][hi][wm0 + l31] : &Bs[0][hi][wn0 + l31];
+    const int lxa = (TRN_OK && LDA != LDB && trn) ? LDB : LDA, lxb = (TRN_OK && LDA != LDB && trn) ? LDA : LDB;     // compile-time constants unless a 1 x 1-tile plan has BM != BN
+
     // software-pipelined operand fetch: the LDS reads of step kk+1 are issued BEFORE the MFMAs of step kk (hipcc otherwise emits
     // read -> s_waitcnt lgkmcnt(0) -> MFMAs per step, exposing the LDS latency whenever a SIMD holds fewer than ~3 waves)
     auto compute = [&](int cur) {
         float a[2][TM], b[2][TN];
+        if constexpr (!TRN_OK) {           // the parent's body: constant offsets into As / Bs
 #pragma unroll
-        for (int t = 0; t < TM; ++t) a[0][t] = As[cur][hi][wm0 + t * 32 + l31];
+            for (int t = 0; t < TM; ++t) a[0][t] = As[cur][hi][wm0 + t * 32 + l31];
 #pragma unroll
-        for (int t = 0; t < TN; ++t) b[0][t] = Bs[cur][hi][wn0 + t * 32 + l31];
+            for (int t = 0; t < TN; ++t) b[0][t] = Bs[cur][hi][wn0 + t * 32 + l31];
 #pragma unroll
-        for (int kk = 0; kk < BK / 2; ++kk) {
-            const int s = kk & 1;
-            if (kk + 1 < BK / 2) {
+            for (int kk = 0; kk < BK / 2; ++kk) {
+                const int s = kk & 1;
+                if (kk + 1 < BK / 2) {
 #pragma unroll
-                for (int t = 0; t < TM; ++t) a[s ^ 1][t] = As[cur][kk * 2 + 2 + hi][wm0 + t * 32 + l31];
+                    for (int t = 0; t < TM; ++t) a[s ^ 1][t] = As[cur][kk * 2 + 2 + hi][wm0 + t * 32 + l31];
 #pragma unroll
-                for (int t = 0; t < TN; ++t) b[s ^ 1][t] = Bs[cur][kk * 2 + 2 + hi][wn0 + t * 32 + l31];
+                    for (int t = 0; t < TN; ++t) b[s ^ 1][t] = Bs[cur][kk * 2 + 2 + hi][wn0 + t * 32 + l31];
+                }
+                TF_SCHED_FENCE();
+#pragma unroll
+                for (int t = 0; t < TM; ++t)
+#pragma unroll
+                    for (int u = 0; u < TN; ++u) mfma_32x32x2(a[s][t], b[s][u], acc[t][u]);
+                TF_SCHED_FENCE();
             }
-            TF_SCHED_FENCE();
+        } else {                           // one tile per wave: fragments through xa / xb
+            const float* pa = xa + cur * BK * lxa;
+            const float* pb = xb + cur * BK * lxb;
+            a[0][0] = pa[0];
+            b[0][0] = pb[0];
 #pragma unroll
-            for (int t = 0; t < TM; ++t)
-#pragma unroll
-                for (int u = 0; u < TN; ++u) mfma_32x32x2(a[s][t], b[s][u], acc[t][u]);
-            TF_SCHED_FENCE();
+            for (int kk = 0; kk < BK / 2; ++kk) {
+                const int s = kk & 1;
+                if (kk + 1 < BK / 2) {
+                    a[s ^ 1][0] = pa[(kk * 2 + 2) * lxa];
+                    b[s ^ 1][0] = pb[(kk * 2 + 2) * lxb];
+                }
+                TF_SCHED_FENCE();
+                mfma_32x32x2(a[s][0], b[s][0], acc[0][0]);
+                TF_SCHED_FENCE();
+            }
         }
     };
 
@@ -593,21 +680,35 @@ __device__ __forceinline__ void gemm_tile(LA& la, LB& lb, const GemmEpi& ep, int
     // the group); operands are read as fp32 from the same K-major tiles and rounded in registers.  Kept in the same kernel behind a
     // block-uniform flag: its extra live registers exist only inside this branch.
     auto compute_bf16 = [&](int cur) {
+        if constexpr (!TRN_OK) {           // the parent's body
 #pragma unroll
-        for (int g = 0; g < BK / 16; ++g) {
-            float a[TM][8], b[TN][8];
+            for (int g = 0; g < BK / 16; ++g) {
+                float a[TM][8], b[TN][8];
 #pragma unroll
-            for (int t = 0; t < TM; ++t)
+                for (int t = 0; t < TM; ++t)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) a[t][j] = As[cur][g * 16 + 8 * hi + j][wm0 + t * 32 + l31];
+                    for (int j = 0; j < 8; ++j) a[t][j] = As[cur][g * 16 + 8 * hi + j][wm0 + t * 32 + l31];
 #pragma unroll
-            for (int t = 0; t < TN; ++t)
+                for (int t = 0; t < TN; ++t)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) b[t][j] = Bs[cur][g * 16 + 8 * hi + j][wn0 + t * 32 + l31];
+                    for (int j = 0; j < 8; ++j) b[t][j] = Bs[cur][g * 16 + 8 * hi + j][wn0 + t * 32 + l31];
 #pragma unroll
-            for (int t = 0; t < TM; ++t)
+                for (int t = 0; t < TM; ++t)
 #pragma unroll
-                for (int u = 0; u < TN; ++u) mfma_32x32x16_lp(a[t], b[u], acc[t][u], ep.prec);
+                    for (int u = 0; u < TN; ++u) mfma_32x32x16_lp(a[t], b[u], acc[t][u], ep.prec);
+            }
+        } else {
+            const float* pa = xa + (cur * BK + 7 * hi) * lxa;       // xa / xb already sit on k row hi
+            const float* pb = xb + (cur * BK + 7 * hi) * lxb;
+#pragma unroll
+            for (int g = 0; g < BK / 16; ++g) {
+                float a[1][8], b[1][8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[0][j] = pa[(g * 16 + j) * lxa];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) b[0][j] = pb[(g * 16 + j) * lxb];
+                mfma_32x32x16_lp(a[0], b[0], acc[0][0], ep.prec);
+            }
         }
     };
     const bool lowp = ep.prec == 1 || ep.prec == 3;      // precision 2 (bf16x3 split) exists in the LDS-DMA kernels only: this kernel then stays on the exact fp32 MFMA
@@ -676,6 +777,9 @@ __device__ __forceinline__ void gemm_tile(LA& la, LB& lb, const GemmEpi& ep, int
         }
     }
 
+    if constexpr (TRN_OK) {
+        if (trn) { gemm_epilogue_t(acc[0][0], ep, M, N, i0, j0, wm0, wn0, z); return; }
+    }
     gemm_epilogue<TM, TN>(acc, ep, M, N, i0, j0, BM, BN, wm0, wn0, z);
 }
 
@@ -805,9 +909,27 @@ inline GemmPlan plan_gemm(int M, int N, int K, int batch, bool allow_splitk) {
     return p;
 }
 
+// 16-byte epilogue on a transposed accumulator (GemmEpi::trn, gemm_epilogue_t).  TF_GEMM_EPI16=0 keeps every launch on the 4-byte epilogue.
+int gemm_epi16();                  // api.cpp: the switch (read once from the environment; tf_gemm_epi16 re-sets it for tests)
+long epi16_count(int add);         // api.cpp: register-staged launches configured with the transposed epilogue so far (tf_gemm_epi16_launches)
+// Eligible: a plan whose waves own ONE 32x32 tile each (64x64 / 2 x 2 waves, 128x32 / 4 x 1 waves) in its 16-byte-operand instantiation, a store or +=
+// epilogue into rows of contiguous columns, and every 4-column group of C / residual / mask / bias 16-byte aligned in every batch.  Anything else
+// takes gemm_epilogue as before.
+inline bool epi16_eligible(const GemmEpi& ep, int N, int BM, int BN, int WAVES_M, bool allvec) {
+    if (!gemm_epi16() || !allvec) return false;
+    if (BM != 32 * WAVES_M || BN * WAVES_M != 32 * 4) return false;
+    if (ep.mode != 0 && ep.mode != 1) return false;
+    if (ep.stat) return false;      // launches that carry BatchNorm statistics keep the column-per-lane form (a column's sum is 32 in-lane adds there)
+    if (ep.ldcj != 1 || (N & 3) || (ep.ldc & 3) || (ep.sc_outer & 3) || (ep.sc_inner & 3) || !aligned16(ep.C)) return false;
+    if (ep.bias && (!aligned16(ep.bias) || (ep.sbias & 3))) return false;
+    if (ep.res && (!aligned16(ep.res) || (ep.ldres & 3))) return false;
+    if (ep.mask && (!aligned16(ep.mask) || (ep.ldmask & 3))) return false;
+    return true;
+}
+
 // grid geometry + launch-time epilogue fields (compute precision, tile rasterisation, number of statistic parts) of one register-staged launch
 struct CfgGeom { int tiles_m, tiles_n, kchunk, nsplit; GemmEpi epg; };
-inline CfgGeom cfg_geom(const GemmEpi& ep, int M, int N, int K, int splitk, int BM, int BN, int BK, int WAVES_M) {
+inline CfgGeom cfg_geom(const GemmEpi& ep, int M, int N, int K, int splitk, int BM, int BN, int BK, int WAVES_M, bool allvec = true) {
     CfgGeom c;
     c.tiles_m = cdiv(M, BM); c.tiles_n = cdiv(N, BN);
     int kchunk = cdiv(cdiv(K, splitk), BK) * BK;
@@ -828,12 +950,14 @@ inline CfgGeom cfg_geom(const GemmEpi& ep, int M, int N, int K, int splitk, int 
         c.epg.group_m = (g >= 2 && c.tiles_n >= 4) ? g : 1;
     }
     if (c.epg.stat_nparts) *c.epg.stat_nparts = c.epg.stat ? cdiv(M, BM / WAVES_M) : 0;
+    c.epg.trn = epi16_eligible(c.epg, N, BM, BN, WAVES_M, allvec) ? 1 : 0;
+    if (c.epg.trn) epi16_count(1);
     return c;
 }
 
 template <int BM, int BN, int WAVES_M, int BK, class LA, bool A_KC, class LB, bool B_KC, int NT = 256, int PF = 1>
 inline void launch_cfg(const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, int splitk, void* stream) {
-    const CfgGeom cg = cfg_geom(ep, M, N, K, splitk, BM, BN, BK, WAVES_M);
+    const CfgGeom cg = cfg_geom(ep, M, N, K, splitk, BM, BN, BK, WAVES_M, la.vec && lb.vec);
     const int tiles_m = cg.tiles_m, tiles_n = cg.tiles_n, kchunk = cg.kchunk;
     dim3 grid(tiles_m * tiles_n, cg.nsplit, batch);
     const GemmEpi& epg = cg.epg;

@@ -296,6 +296,18 @@ def force_plan(bm=0, bn=0, bk=0, splitk=1):
     check(L().tf_force_plan(bm, bn, bk, splitk), "tf_force_plan")
 
 
+def gemm_epi16(on=None):
+    """Tests / labs: the 16-byte (transposed-accumulator) epilogue switch of the register-staged GEMM engine.  ``True`` / ``False`` set it,
+    ``None`` re-reads TF_GEMM_EPI16 from the environment; returns the value now in force."""
+    return bool(L().tf_gemm_epi16(-1 if on is None else int(bool(on))))
+
+
+def gemm_epi16_launches():
+    """Launches configured with the 16-byte epilogue so far (a query: a call that is not eligible takes the 4-byte epilogue silently)."""
+    L().tf_gemm_epi16_launches.restype = ctypes.c_long
+    return L().tf_gemm_epi16_launches()
+
+
 def force_dma(kind, splitk=1):
     """tests: pin LDS-DMA GEMM configuration ``kind`` (1..5); calls that are not eligible (unaligned / non-plain operands) keep the heuristic."""
     check(L().tf_force_dma(kind, splitk), "tf_force_dma")
