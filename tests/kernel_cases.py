@@ -280,6 +280,49 @@ def check_bn_se_consumer_fusion(dev, B=3, H=6, W=10, C=48, Cr=12):
     close(dgm2, grads[1], tol=1e-4, what="folded bn dgamma"); close(dbt2, grads[2], tol=1e-4, what="folded bn dbeta")
 
 
+# the vector path with several row chunks; C % 4 != 0 twice (the scalar <1> kernels, which no other case reaches through these entry points); a single row
+BN_VARIANT_CASES = [(3, 6, 10, 48), (2, 3, 5, 6), (1, 4, 5, 7), (1, 1, 1, 8)]
+
+
+def check_bn_variants_bitwise(dev, B, H, W, C):
+    """The fused BatchNorm / SE passes recompute what the unfused ones store (the ReLU mask from y * scale + shift, the SE scale's input gradient): on the
+    chunk-partials path (no atomics) each fused op must equal the composition of the unfused ops it replaces BIT FOR BIT."""
+    old_dbg = ops._DBG_LEGACY_BNB
+    ops._DBG_LEGACY_BNB = True
+    try:
+        rows = B * H * W
+        y = R(B, H, W, C, dev=dev, scale=1.5)
+        gamma, beta = R(C, seed=1, dev=dev).abs() + 0.5, R(C, seed=2, dev=dev) * 0.3
+        gate, dmean = R(B, C, seed=3, dev=dev), R(B, C, seed=4, dev=dev)
+        dzs = R(B, H, W, C, seed=5, dev=dev)
+        # statistics as a producer's epilogue would have written them (one part = the whole tensor, Welford triple)
+        cs = ops.ColStat(rows, C, dev, max_parts=1)
+        y2 = y.reshape(rows, C)
+        m = y2.mean(0)
+        cs.buf[:C] = rows; cs.buf[C:2 * C] = m; cs.buf[2 * C:] = ((y2 - m) ** 2).sum(0)
+        cs.nparts.value = 1
+        rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+        z, sm, si = ops.bn_fwd_parts(y, cs, gamma, beta, rm.clone(), rv.clone(), None, True)
+        coef, sm2, si2 = ops.bn_finalize_parts(cs, gamma, beta, rm.clone(), rv.clone())
+        assert torch.equal(sm, sm2) and torch.equal(si, si2), "finalize: save_mean / save_invstd"
+        assert torch.equal(ops.se_scale_bn_fwd(y, coef, gate), ops.se_scale_fwd(z, gate)), "se_scale_bn_fwd != se_scale_fwd(bn_fwd_parts)"
+        # BatchNorm backward: mask recomputed from y against the mask of the stored z
+        dg0, db0, dg1, db1, dg2, db2 = (torch.zeros(C, device=dev) for _ in range(6))
+        dx0, _ = ops.bn_bwd(dzs, z, y, gamma, sm, si, dg0, db0)
+        dx1 = ops.bn_bwd_remask(dzs, y, coef, gamma, sm, si, dg1, db1)
+        assert torch.equal(dx1, dx0), "bn_bwd_remask dx != bn_bwd dx"
+        assert torch.equal(dg1, dg0) and torch.equal(db1, db0), "bn_bwd_remask dgamma / dbeta != bn_bwd"
+        # ... with the SE scale's backward folded in, against the two passes it replaces
+        dz = ops.se_scale_bwd_x(dzs, gate, dmean, y.shape)
+        dg1.zero_(); db1.zero_()
+        dx1 = ops.bn_bwd_remask(dz, y, coef, gamma, sm, si, dg1, db1)
+        dx2 = ops.bn_bwd_remask_se(dzs, gate, dmean, y, coef, gamma, sm, si, dg2, db2)
+        assert torch.equal(dx2, dx1), "bn_bwd_remask_se dx != bn_bwd_remask(se_scale_bwd_x) dx"
+        assert torch.equal(dg2, dg1) and torch.equal(db2, db1), "bn_bwd_remask_se dgamma / dbeta != bn_bwd_remask(se_scale_bwd_x)"
+    finally:
+        ops._DBG_LEGACY_BNB = old_dbg
+
+
 def check_convnext_pieces(dev):
     """ConvNeXt block pieces (csrc/convnext.cpp; timm convnext_*, transfuser.py:395-416): depthwise 7x7 (+ bias) forward / input gradient (flipped
     taps, accumulate) / weight + bias gradient, exact GELU forward / backward, layer scale + shortcut, column sum of a product, the 4x4 / s4 patchify

@@ -225,6 +225,11 @@ def test_bn_apply_folded_into_se_consumers(case):
     kc.check_bn_se_consumer_fusion("cpu", *case)
 
 
+@pytest.mark.parametrize("case", kc.BN_VARIANT_CASES, ids=str)
+def test_fused_bn_se_passes_equal_the_unfused_ones_bitwise(case):
+    kc.check_bn_variants_bitwise("cpu", *case)
+
+
 def test_convnext_block_pieces():
     kc.check_convnext_pieces("cpu")
 

@@ -2,6 +2,7 @@
 """Per-kernel summary of a rocprofv3 --kernel-trace CSV of bench.py (hipGraph replay): ms per training step, launches per step, average us,
 for the LAST full steps (delimited by adamw_kernel launches), plus GPU-busy (union of kernel intervals) vs wall.  python tools/trace_csv_stats.py <dir>"""
 import collections, csv, glob, json, os, sys
+from trace_families import is_batchnorm, is_se
 if len(sys.argv) > 2:       # the traced bench.py run's stdout: its JSON line names the library that was traced (bench.py only trusts a summary of ITS build)
     try:
         line = [l for l in open(sys.argv[2]).read().splitlines() if l.startswith("{")][-1]
@@ -33,7 +34,7 @@ for name, s, e in seg:
 fam = collections.defaultdict(float)
 for name, (c, t, _, _) in agg.items():
     key = "gemm engine (gemm_kernel / gemm_pair_kernel / gemm_dma_kernel)" if "gemm_kernel" in name or "gemm_dma" in name or "gemm_pair" in name else "direct conv (conv3x3_grouped / conv3x3_small / conv3x3_thin)" if ("conv3x3_small" in name or "conv3x3_grouped" in name or "conv3x3_thin" in name) else \
-        "batchnorm" if ("bn_" in name or "BnStat" in name or "BnBwd" in name) else "other"
+        "batchnorm" if is_batchnorm(name) else "se" if is_se(name) else "other"
     fam[key] += t / n / 1e6
 print("families (ms/step):", ", ".join("%s %.2f" % kv for kv in sorted(fam.items(), key=lambda kv: -kv[1])))
 print("per kernel (ms/step, calls/step, avg us, min us, max us):")

@@ -4,6 +4,7 @@ launches) is cut at every kernel start / end; each slice of wall time is charged
 to "idle" when none is.  Per kernel name: charged wall ms, the part of it spent running ALONE (nothing else on the chip: shortening the kernel
 shortens the step one for one), launches.  Also per queue: busy time.   python tools/trace_timeline.py <dir> [steps]"""
 import collections, csv, glob, os, sys
+from trace_families import is_batchnorm, is_se
 f = glob.glob(os.path.join(sys.argv[1], "*kernel_trace.csv"))[0]
 rd = list(csv.DictReader(open(f)))
 qk = "Queue_Id" if "Queue_Id" in rd[0] else None
@@ -43,7 +44,7 @@ qb = collections.defaultdict(float)
 for name, s, e, q in seg: qb[q] += e - s
 print("per queue busy ms/step:", ", ".join("%s: %.2f" % (q, v / n / 1e6) for q, v in sorted(qb.items(), key=lambda kv: -kv[1])))
 fam = lambda name: ("gemm engine" if "gemm_kernel" in name or "gemm_dma" in name or "gemm_pair" in name else "grouped conv" if "conv3x3_grouped" in name else "direct conv" if ("conv3x3_small" in name or "conv3x3_thin" in name or "stem_direct" in name) else
-                    "batchnorm" if ("bn_" in name or "BnStat" in name or "BnBwd" in name or "BnRelu" in name) else "attention" if "attention" in name else "se" if "se_" in name or "SeGate" in name else "adamw" if "adamw" in name else "other")
+                    "batchnorm" if is_batchnorm(name) else "attention" if "attention" in name else "se" if is_se(name) else "adamw" if "adamw" in name else "other")
 fc = collections.defaultdict(float); fs = collections.defaultdict(float)
 for name in charged: fc[fam(name)] += charged[name]; fs[fam(name)] += solo[name]
 print("families: charged wall ms (of which alone):", ", ".join("%s %.2f (%.2f)" % (k, v / n / 1e6, fs[k] / n / 1e6) for k, v in sorted(fc.items(), key=lambda kv: -kv[1])))

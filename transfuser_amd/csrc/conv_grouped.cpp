@@ -93,8 +93,7 @@ __device__ __forceinline__ void store_patch_slot(float* patch, int s, const floa
 // block's group in LDS; zero padding stays zero (the transform is applied to pixels inside the map only).
 __device__ __forceinline__ float4 bnrelu4(const float4 v, const float* cf, int c, bool ok) {
     if (!ok) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return make_float4(fmaxf(v.x * cf[c] + cf[CG + c], 0.f), fmaxf(v.y * cf[c + 1] + cf[CG + c + 1], 0.f), fmaxf(v.z * cf[c + 2] + cf[CG + c + 2], 0.f),
-                       fmaxf(v.w * cf[c + 3] + cf[CG + c + 3], 0.f));
+    return make_float4(bn_relu(v.x, cf[c], cf[CG + c]), bn_relu(v.y, cf[c + 1], cf[CG + c + 1]), bn_relu(v.z, cf[c + 2], cf[CG + c + 2]), bn_relu(v.w, cf[c + 3], cf[CG + c + 3]));
 }
 __device__ __forceinline__ void stage_group_coef(float* cf, const float* __restrict__ in_coef, int coff, int C) {
     if (in_coef && threadIdx.x < 2 * CG) cf[threadIdx.x] = in_coef[threadIdx.x < CG ? coff + threadIdx.x : C + coff + threadIdx.x - CG];

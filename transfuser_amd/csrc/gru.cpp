@@ -16,8 +16,6 @@ constexpr int GH = 64;       // config.gru_hidden_size
 constexpr int GMAXB = 32;
 constexpr int GMAXIN = 4;
 
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
 // cache layout (floats): hs[(P+1)][B][64] | gates[P][B][4][64] (r, z, n, gh_n) | xin[P][B][4]
 __global__ void __launch_bounds__(256) gru_wp_fwd_kernel(const float* __restrict__ z0, const float* __restrict__ tp, const float* __restrict__ w_ih,
                                                          const float* __restrict__ w_hh, const float* __restrict__ b_ih, const float* __restrict__ b_hh,

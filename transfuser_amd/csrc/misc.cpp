@@ -24,7 +24,7 @@ __global__ void __launch_bounds__(256) axpby_kernel(const float* __restrict__ a,
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = alpha * a[i] + (b ? beta * b[i] : 0.f);
 }
 __global__ void __launch_bounds__(256) sigmoid_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = 1.f / (1.f + expf(-x[i]));
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = sigmoidf_(x[i]);
 }
 // dropout with our counter-based RNG: y = keep ? x / (1-p) : 0 ; same call regenerates the mask in backward
 __global__ void __launch_bounds__(256) dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long n, const uint32_t* __restrict__ seed,

@@ -26,6 +26,56 @@ template <int V> __device__ __forceinline__ void stv(float* p, const vecf<V>& a)
     else *p = a.v[0];
 }
 
+// ---- the per-element expressions of the BatchNorm / Squeeze-Excite passes over vecf<V> (their scalars: tf_prims.h).  Each is written HERE once and called
+// by every reduction functor, element-wise functor and column-owned kernel that needs it: a value one pass stores and another recomputes is the same
+// bits by construction, not by keeping hand-written copies in step.
+// y = x sc + sh (+ res) (relu); res = the address of this vector's residual or NULL
+template <int V> __device__ __forceinline__ vecf<V> bn_apply(const vecf<V>& x, const vecf<V>& sc, const vecf<V>& sh, bool relu, const float* res = nullptr) {
+    vecf<V> r, rr;
+    if (res) rr = ldv<V>(res);
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        float v = bn_affine(x.v[i], sc.v[i], sh.v[i]);
+        if (res) v += rr.v[i];
+        r.v[i] = relu ? fmaxf(v, 0.f) : v;
+    }
+    return r;
+}
+// g [v > 0]: a gradient behind a ReLU, v = the ReLU's output or its input (the two masks agree)
+template <int V> __device__ __forceinline__ vecf<V> relu_mask(const vecf<V>& g, const vecf<V>& v) {
+    vecf<V> r;
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.v[i] = tf::relu_mask(g.v[i], v.v[i]);
+    return r;
+}
+// BatchNorm backward: dx = A g + Bc x + Cc (the coefficients bn_bwd_finalize_kernel derives from sum g, sum g xhat)
+template <int V> __device__ __forceinline__ vecf<V> bn_bwd_dx(const vecf<V>& g, const vecf<V>& x, const vecf<V>& A, const vecf<V>& Bc, const vecf<V>& Cc) {
+    vecf<V> r;
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.v[i] = A.v[i] * g.v[i] + Bc.v[i] * x.v[i] + Cc.v[i];
+    return r;
+}
+// x sigmoid(gate)
+template <int V> __device__ __forceinline__ vecf<V> se_scale(const vecf<V>& x, const vecf<V>& gate) {
+    vecf<V> r;
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.v[i] = x.v[i] * sigmoidf_(gate.v[i]);
+    return r;
+}
+// the SE scale's input gradient dy sigmoid(gate) + dmean inv_hw; a term that is absent (the backward of a global average pool has no dy) is not read
+template <int V> __device__ __forceinline__ vecf<V> se_bwd_grad(const vecf<V>& dy, const vecf<V>& gate, const vecf<V>& dmean, float inv_hw, bool has_dy = true,
+                                                                bool has_dmean = true) {
+    vecf<V> r;
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.v[i] = 0.f;
+    if (has_dy) r = se_scale(dy, gate);
+    if (has_dmean) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) r.v[i] += dmean.v[i] * inv_hw;
+    }
+    return r;
+}
+
 constexpr int kBnSlots = 16;    // accumulator copies of the atomically accumulated BatchNorm statistics
 constexpr int kMaxChunks = 512;   // finalize is wave-parallel over chunks, so many small partials are cheap
 constexpr long kWsFloats = 4L << 20;  // 16 MiB workspace (floats), see tf_workspace_bytes()
@@ -59,96 +109,81 @@ inline void cap_chunks(RedPlan& p, int rows, int maxc) {
     if (p.nchunks > maxc) { p.rows_per_chunk = cdiv(rows, maxc); p.nchunks = cdiv(rows, p.rows_per_chunk); }
 }
 
-// ---- functors: eval(global_row, c, out[NACC]) ------------------------------------------------
-template <int V> struct SumF {
-    const float* x; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const { o[0] = ldv<V>(x + row * C + c); }
-};
-template <int V> struct BnStatF {  // shifted moments: d = x - K[c]
+// ---- functors: eval(global_row, c, out[NACC]); the vector width V is the kernel's (deduced from out), so ONE object serves the <4> and the <1> launch ----
+struct BnStatF {  // shifted moments: d = x - K[c]
     const float* x; const float* K; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
         vecf<V> a = ldv<V>(x + row * C + c), k = ldv<V>(K + c);
 #pragma unroll
         for (int i = 0; i < V; ++i) { float d = a.v[i] - k.v[i]; o[0].v[i] = d; o[1].v[i] = d * d; }
     }
 };
-template <int V> struct BnBwdF {  // g = dz * [z > 0]; (g, g * xhat)
-    const float* dz; const float* z; const float* x; const float* mean; const float* invstd; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
-        vecf<V> g = ldv<V>(dz + row * C + c), a = ldv<V>(x + row * C + c), m = ldv<V>(mean + c), s = ldv<V>(invstd + c);
-        if (z) { vecf<V> zz = ldv<V>(z + row * C + c);
-#pragma unroll
-            for (int i = 0; i < V; ++i) if (!(zz.v[i] > 0.f)) g.v[i] = 0.f; }
-#pragma unroll
-        for (int i = 0; i < V; ++i) { o[0].v[i] = g.v[i]; o[1].v[i] = g.v[i] * ((a.v[i] - m.v[i]) * s.v[i]); }
-    }
-};
-template <int V> struct MulF {  // dy * x (SE gate gradient), optional relu mask y on dy
+struct MulF {  // dy * x (SE gate gradient), optional relu mask y on dy
     const float* dy; const float* x; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
         vecf<V> a = ldv<V>(dy + row * C + c), b = ldv<V>(x + row * C + c);
 #pragma unroll
         for (int i = 0; i < V; ++i) o[0].v[i] = a.v[i] * b.v[i];
     }
 };
-template <int V> struct MaskSumF {  // dy * [y > 0] (bias gradient behind a fused bias+ReLU epilogue)
+struct MaskSumF {  // dy * [y > 0] (bias gradient behind a fused bias+ReLU epilogue)
     const float* dy; const float* y; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
-        vecf<V> a = ldv<V>(dy + row * C + c);
-        if (y) { vecf<V> b = ldv<V>(y + row * C + c);
-#pragma unroll
-            for (int i = 0; i < V; ++i) if (!(b.v[i] > 0.f)) a.v[i] = 0.f; }
-        o[0] = a;
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+        const vecf<V> a = ldv<V>(dy + row * C + c);
+        o[0] = y ? relu_mask(a, ldv<V>(y + row * C + c)) : a;
     }
 };
 
 // ---- BatchNorm apply folded into its CONSUMERS (the conv2 -> BN -> ReLU -> SE part of a RegNetY bottleneck): z = max(x sc + sh, 0) is
 // recomputed from the convolution output x and the layer's (scale | shift) wherever it is needed and never written to memory.
-// The expression is the one bn_apply_kernel evaluates (multiply, then add: -ffp-contract=off), so a recomputed ReLU mask is bit-identical.
-template <int V> struct BnReluSumF {   // SE squeeze of the BN + ReLU output
+// Every pass evaluates it through bn_apply / bn_affine (multiply, then add: -ffp-contract=off), so a recomputed ReLU mask is bit-identical.
+struct BnReluSumF {   // SE squeeze of the BN + ReLU output
     const float* x; const float* coef; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
-        vecf<V> a = ldv<V>(x + row * C + c), sc = ldv<V>(coef + c), sh = ldv<V>(coef + C + c);
-#pragma unroll
-        for (int i = 0; i < V; ++i) o[0].v[i] = fmaxf(a.v[i] * sc.v[i] + sh.v[i], 0.f);
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+        o[0] = bn_apply(ldv<V>(x + row * C + c), ldv<V>(coef + c), ldv<V>(coef + C + c), true);
     }
 };
-template <int V> struct BnReluMulF {   // SE gate gradient: dy * z
+struct BnReluMulF {   // SE gate gradient: dy * z
     const float* dy; const float* x; const float* coef; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
-        vecf<V> g = ldv<V>(dy + row * C + c), a = ldv<V>(x + row * C + c), sc = ldv<V>(coef + c), sh = ldv<V>(coef + C + c);
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+        const vecf<V> g = ldv<V>(dy + row * C + c), z = bn_apply(ldv<V>(x + row * C + c), ldv<V>(coef + c), ldv<V>(coef + C + c), true);
 #pragma unroll
-        for (int i = 0; i < V; ++i) o[0].v[i] = g.v[i] * fmaxf(a.v[i] * sc.v[i] + sh.v[i], 0.f);
-    }
-};
-template <int V> struct BnBwdRemaskF {  // BnBwdF with the ReLU mask recomputed from x: g = dz * [x sc + sh > 0]; (g, g * xhat)
-    const float* dz; const float* x; const float* coef; const float* mean; const float* invstd; int C;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
-        vecf<V> g = ldv<V>(dz + row * C + c), a = ldv<V>(x + row * C + c), m = ldv<V>(mean + c), s = ldv<V>(invstd + c), sc = ldv<V>(coef + c), sh = ldv<V>(coef + C + c);
-#pragma unroll
-        for (int i = 0; i < V; ++i) {
-            if (!(a.v[i] * sc.v[i] + sh.v[i] > 0.f)) g.v[i] = 0.f;
-            o[0].v[i] = g.v[i];
-            o[1].v[i] = g.v[i] * ((a.v[i] - m.v[i]) * s.v[i]);
-        }
+        for (int i = 0; i < V; ++i) o[0].v[i] = g.v[i] * z.v[i];
     }
 };
 
-// BnBwdRemaskF with the SE scale's backward folded in: the incoming gradient is dz = dy * sigmoid(gate[b][c]) + dmean[b][c] * inv_hw (tf_se_scale_bwd_x_f32),
+// ---- the three sources of a BatchNorm backward's incoming gradient g.  at(o, row, c, x) = the vector at element offset o = row C + c, where the
+// BatchNorm's input is x.  The reduction functor (BnBwdF) and the apply functor (BnBwdApplyF) of one backward are instantiated over the SAME source.
+struct GradZ {          // g = dz [z > 0], z = the stored output behind the ReLU (NULL: no ReLU)
+    const float* dz; const float* z;
+    template <int V> __device__ __forceinline__ vecf<V> at(long o, int, int, const vecf<V>&) const {
+        const vecf<V> g = ldv<V>(dz + o);
+        return z ? relu_mask(g, ldv<V>(z + o)) : g;
+    }
+};
+struct GradRemask {     // g = dz [x sc + sh > 0]: the ReLU's output was never stored, fcoef = the forward's (scale | shift)
+    const float* dz; const float* fcoef; int C;
+    template <int V> __device__ __forceinline__ vecf<V> at(long o, int, int c, const vecf<V>& x) const {
+        return relu_mask(ldv<V>(dz + o), bn_apply(x, ldv<V>(fcoef + c), ldv<V>(fcoef + C + c), false));
+    }
+};
+// GradRemask with the SE scale's backward folded in: the incoming gradient is dz = dy * sigmoid(gate[b][c]) + dmean[b][c] * inv_hw (tf_se_scale_bwd_x_f32),
 // recomputed here instead of being written by its own pass; rows are sample-major (b = row / HW)
-template <int V> struct SeBnBwdRemaskF {
-    const float* dy; const float* gate; const float* dmean; const float* x; const float* coef; const float* mean; const float* invstd; int C; int HW; float inv_hw;
-    __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
-        const long bc = (row / HW) * C + c;
-        vecf<V> g = ldv<V>(dy + row * C + c), a = ldv<V>(x + row * C + c), m = ldv<V>(mean + c), s = ldv<V>(invstd + c), sc = ldv<V>(coef + c), sh = ldv<V>(coef + C + c);
-        vecf<V> gt = ldv<V>(gate + bc), dm = ldv<V>(dmean + bc);
+struct GradRemaskSe {
+    const float* dy; const float* gate; const float* dmean; const float* fcoef; int C; int HW; float inv_hw;
+    template <int V> __device__ __forceinline__ vecf<V> at(long o, int row, int c, const vecf<V>& x) const {
+        const long bc = (long)(row / HW) * C + c;
+        const vecf<V> dz = se_bwd_grad(ldv<V>(dy + o), ldv<V>(gate + bc), ldv<V>(dmean + bc), inv_hw);
+        return relu_mask(dz, bn_apply(x, ldv<V>(fcoef + c), ldv<V>(fcoef + C + c), false));
+    }
+};
+template <class G> struct BnBwdF {  // (g, g * xhat)
+    G grad; const float* x; const float* mean; const float* invstd; int C;
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+        const long e = row * C + c;
+        const vecf<V> a = ldv<V>(x + e), m = ldv<V>(mean + c), s = ldv<V>(invstd + c), g = grad.at(e, (int)row, c, a);
 #pragma unroll
-        for (int i = 0; i < V; ++i) {
-            float gi = g.v[i] * (1.f / (1.f + expf(-gt.v[i]))) + dm.v[i] * inv_hw;
-            if (!(a.v[i] * sc.v[i] + sh.v[i] > 0.f)) gi = 0.f;
-            o[0].v[i] = gi;
-            o[1].v[i] = gi * ((a.v[i] - m.v[i]) * s.v[i]);
-        }
+        for (int i = 0; i < V; ++i) { o[0].v[i] = g.v[i]; o[1].v[i] = g.v[i] * ((a.v[i] - m.v[i]) * s.v[i]); }
     }
 };
 
@@ -234,14 +269,13 @@ __global__ void __launch_bounds__(256) colreduce_kernel(F f, int rows_per_seg, i
     }
 }
 
-template <int NACC, class F4, class F1>
-inline void launch_reduce(const RedPlan& p, const F4& f4, const F1& f1, int rows_per_seg, int C, int nseg, float* ws, void* stream, int atomic = 0,
-                          float scale = 1.f) {
+template <int NACC, class F>
+inline void launch_reduce(const RedPlan& p, const F& f, int rows_per_seg, int C, int nseg, float* ws, void* stream, int atomic = 0, float scale = 1.f) {
     dim3 grid(p.coltiles, p.nchunks, nseg);
     static const bool unroll = [] { const char* e = getenv("TF_COLREDUCE_UNROLL"); return e ? e[0] != '0' : true; }();
     if (!unroll && atomic == 0) atomic = -1;
-    if (p.V == 4) TF_LAUNCH((colreduce_kernel<4, NACC, F4>), grid, dim3(256), stream, f4, rows_per_seg, C, p.CTV, p.rows_per_chunk, ws, atomic, scale);
-    else TF_LAUNCH((colreduce_kernel<1, NACC, F1>), grid, dim3(256), stream, f1, rows_per_seg, C, p.CTV, p.rows_per_chunk, ws, atomic, scale);
+    if (p.V == 4) TF_LAUNCH((colreduce_kernel<4, NACC, F>), grid, dim3(256), stream, f, rows_per_seg, C, p.CTV, p.rows_per_chunk, ws, atomic, scale);
+    else TF_LAUNCH((colreduce_kernel<1, NACC, F>), grid, dim3(256), stream, f, rows_per_seg, C, p.CTV, p.rows_per_chunk, ws, atomic, scale);
 }
 
 
@@ -416,48 +450,67 @@ __global__ void __launch_bounds__(256) se_bwd_finalize_kernel(const float* __res
     const int seg = live ? i / C : 0, c = live ? i - seg * C : 0;
     const float s = chunk_sum(ws + (long)seg * nch * C + c, C, nch, lane, live);
     if (live && lane == 0) {
-        const float sg = 1.f / (1.f + expf(-gate[i]));
+        const float sg = sigmoidf_(gate[i]);
         dgate[i] = s * sg * (1.f - sg);
     }
 }
 
-// ---- per-channel elementwise passes (grid-stride over vectors) ------------------------------------
-template <int V>
-__global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ coef, const float* __restrict__ res,
-                                                       float* __restrict__ y, long nvec, int C, int relu) {
-    const int cv = C / V;
+// ---- per-channel elementwise passes: ONE grid-stride loop over the vectors of a (rows x C) matrix.  A functor evaluates the vector at element offset
+// o = row C + c ONCE into r (whose width is the kernel's V), and does its own stores (an fp32 destination may be NULL where only a 16-bit copy is wanted).
+// ew_kernel drops r, tile16_kernel below packs it: a 16-bit copy is cast16 of the fp32 kernel's output because both ARE the same functor.
+template <int V, class F>
+__global__ void __launch_bounds__(256) ew_kernel(F f, long nvec) {
+    const int cv = f.C / V;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % cv) * V;
-        vecf<V> a = ldv<V>(x + i * V), s = ldv<V>(coef + c), t = ldv<V>(coef + C + c);
         vecf<V> r;
-        if (res) r = ldv<V>(res + i * V);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            float v = a.v[k] * s.v[k] + t.v[k];
-            if (res) v += r.v[k];
-            if (relu) v = fmaxf(v, 0.f);
-            a.v[k] = v;
-        }
-        stv<V>(y + i * V, a);
+        f(i * V, (int)(i / cv), (int)(i % cv) * V, r);
     }
 }
-template <int V>
-__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restrict__ dz, const float* __restrict__ z, const float* __restrict__ x,
-                                                           const float* __restrict__ coef, float* __restrict__ dx, float* __restrict__ dres,
-                                                           long nvec, int C) {
-    const int cv = C / V;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % cv) * V;
-        vecf<V> g = ldv<V>(dz + i * V), a = ldv<V>(x + i * V), A = ldv<V>(coef + c), Bc = ldv<V>(coef + C + c), Cc = ldv<V>(coef + 2 * C + c);
-        if (z) { vecf<V> zz = ldv<V>(z + i * V);
-#pragma unroll
-            for (int k = 0; k < V; ++k) if (!(zz.v[k] > 0.f)) g.v[k] = 0.f; }
-        if (dres) stv<V>(dres + i * V, g);
-#pragma unroll
-        for (int k = 0; k < V; ++k) a.v[k] = A.v[k] * g.v[k] + Bc.v[k] * a.v[k] + Cc.v[k];
-        stv<V>(dx + i * V, a);
+struct BnApplyF {        // y = x sc + sh (+ res) (relu), coef = [sc | sh]
+    const float* x; const float* coef; const float* res; float* y; int C; int relu;
+    template <int V> __device__ __forceinline__ void operator()(long o, int, int c, vecf<V>& r) const {
+        r = bn_apply(ldv<V>(x + o), ldv<V>(coef + c), ldv<V>(coef + C + c), relu != 0, res ? res + o : nullptr);
+        if (y) stv<V>(y + o, r);
     }
-}
+};
+struct SeScaleF {        // y = x * sigmoid(gate[b][c]), b = row / HW
+    const float* x; const float* gate; float* y; int C; int HW;
+    template <int V> __device__ __forceinline__ void operator()(long o, int row, int c, vecf<V>& r) const {
+        r = se_scale(ldv<V>(x + o), ldv<V>(gate + (long)(row / HW) * C + c));
+        stv<V>(y + o, r);
+    }
+};
+struct SeScaleBnF {      // y = max(x sc + sh, 0) * sigmoid(gate[b][c]): BatchNorm apply + ReLU + SE scale in one pass (the BN output itself is never stored)
+    const float* x; const float* coef; const float* gate; float* y; int C; int HW;
+    template <int V> __device__ __forceinline__ void operator()(long o, int row, int c, vecf<V>& r) const {
+        const vecf<V> g = ldv<V>(gate + (long)(row / HW) * C + c);
+        r = se_scale(bn_apply(ldv<V>(x + o), ldv<V>(coef + c), ldv<V>(coef + C + c), true), g);
+        if (y) stv<V>(y + o, r);
+    }
+};
+struct SeBwdApplyF {     // dx (+)= dy * sigmoid(gate[b][c]) + dmean[b][c] * inv_hw      (either term optional)
+    const float* dy; const float* gate; const float* dmean; float* dx; int C; int HW; float inv_hw; int accumulate;
+    template <int V> __device__ __forceinline__ void operator()(long o, int row, int c, vecf<V>& r) const {
+        const long bc = (long)(row / HW) * C + c;
+        vecf<V> a, g, m;
+        if (dy) { a = ldv<V>(dy + o); g = ldv<V>(gate + bc); }
+        if (dmean) m = ldv<V>(dmean + bc);
+        r = se_bwd_grad(a, g, m, inv_hw, dy != nullptr, dmean != nullptr);
+        if (accumulate) { const vecf<V> p = ldv<V>(dx + o);
+#pragma unroll
+            for (int k = 0; k < V; ++k) r.v[k] += p.v[k]; }
+        stv<V>(dx + o, r);
+    }
+};
+template <class G> struct BnBwdApplyF {   // g from the source G (-> dres when not NULL), dx = A g + Bc x + Cc with coef = [A | Bc | Cc]
+    G grad; const float* x; const float* coef; float* dx; float* dres; int C;
+    template <int V> __device__ __forceinline__ void operator()(long o, int row, int c, vecf<V>& r) const {
+        const vecf<V> a = ldv<V>(x + o), A = ldv<V>(coef + c), Bc = ldv<V>(coef + C + c), Cc = ldv<V>(coef + 2 * C + c), g = grad.at(o, row, c, a);
+        if (dres) stv<V>(dres + o, g);
+        r = bn_bwd_dx(g, a, A, Bc, Cc);
+        if (dx) stv<V>(dx + o, r);
+    }
+};
 // ---- single-pass-after-reduce BatchNorm: the statistics were ACCUMULATED with atomics into acc = [S1 | S2] (2*C floats), so there is
 // no finalize kernel: threads own a fixed channel group (the colreduce thread layout), derive its scale / shift from the sums once,
 // then stream their rows.  The chunk-0 block of every column tile also writes save_mean / save_invstd and the running statistics.
@@ -499,16 +552,7 @@ __global__ void __launch_bounds__(256) bn_apply_cols_kernel(const float* __restr
     if (r1 > rows) r1 = rows;
     for (int r = r0 + rl; r < r1; r += rpp) {
         const long o = (long)r * C + c;
-        vecf<V> a = ldv<V>(x + o), rr;
-        if (res) rr = ldv<V>(res + o);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            float v = a.v[k] * sc.v[k] + sh.v[k];
-            if (res) v += rr.v[k];
-            if (relu) v = fmaxf(v, 0.f);
-            a.v[k] = v;
-        }
-        stv<V>(y + o, a);
+        stv<V>(y + o, bn_apply(ldv<V>(x + o), sc, sh, relu != 0, res ? res + o : nullptr));
     }
 }
 // acc = [sum g | sum g*xhat]; dx = A*g + Bc*x + Cc; dgamma += sum g*xhat, dbeta += sum g (chunk-0 blocks)
@@ -541,106 +585,9 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_cols_kernel(const float* __r
     if (r1 > rows) r1 = rows;
     for (int r = r0 + rl; r < r1; r += rpp) {
         const long o = (long)r * C + c;
-        vecf<V> g = ldv<V>(dz + o), a = ldv<V>(x + o);
-        if (z) { vecf<V> zz = ldv<V>(z + o);
-#pragma unroll
-            for (int k = 0; k < V; ++k) if (!(zz.v[k] > 0.f)) g.v[k] = 0.f; }
+        const vecf<V> a = ldv<V>(x + o), g = GradZ{dz, z}.at(o, r, c, a);
         if (dres) stv<V>(dres + o, g);
-#pragma unroll
-        for (int k = 0; k < V; ++k) a.v[k] = A.v[k] * g.v[k] + Bc.v[k] * a.v[k] + Cc.v[k];
-        stv<V>(dx + o, a);
-    }
-}
-// y = x * sigmoid(gate[b][c])
-template <int V>
-__global__ void __launch_bounds__(256) se_scale_kernel(const float* __restrict__ x, const float* __restrict__ gate, float* __restrict__ y, long nvec,
-                                                       int C, long vec_per_b) {
-    const int cv = C / V;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % cv) * V;
-        const long b = i / vec_per_b;
-        vecf<V> a = ldv<V>(x + i * V), g = ldv<V>(gate + b * C + c);
-#pragma unroll
-        for (int k = 0; k < V; ++k) a.v[k] = a.v[k] * (1.f / (1.f + expf(-g.v[k])));
-        stv<V>(y + i * V, a);
-    }
-}
-// y = max(x sc + sh, 0) * sigmoid(gate[b][c]): BatchNorm apply + ReLU + SE scale in one pass (the BN output itself is never stored)
-template <int V>
-__global__ void __launch_bounds__(256) se_scale_bn_kernel(const float* __restrict__ x, const float* __restrict__ coef, const float* __restrict__ gate,
-                                                          float* __restrict__ y, long nvec, int C, long vec_per_b) {
-    const int cv = C / V;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % cv) * V;
-        const long b = i / vec_per_b;
-        vecf<V> a = ldv<V>(x + i * V), g = ldv<V>(gate + b * C + c), sc = ldv<V>(coef + c), sh = ldv<V>(coef + C + c);
-#pragma unroll
-        for (int k = 0; k < V; ++k) a.v[k] = fmaxf(a.v[k] * sc.v[k] + sh.v[k], 0.f) * (1.f / (1.f + expf(-g.v[k])));
-        stv<V>(y + i * V, a);
-    }
-}
-// bn_bwd_apply_kernel with the ReLU mask recomputed from x and the forward (scale | shift)
-template <int V>
-__global__ void __launch_bounds__(256) bn_bwd_apply_remask_kernel(const float* __restrict__ dz, const float* __restrict__ x, const float* __restrict__ fcoef,
-                                                                  const float* __restrict__ coef, float* __restrict__ dx, long nvec, int C) {
-    const int cv = C / V;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % cv) * V;
-        vecf<V> g = ldv<V>(dz + i * V), a = ldv<V>(x + i * V), A = ldv<V>(coef + c), Bc = ldv<V>(coef + C + c), Cc = ldv<V>(coef + 2 * C + c);
-        vecf<V> sc = ldv<V>(fcoef + c), sh = ldv<V>(fcoef + C + c);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            if (!(a.v[k] * sc.v[k] + sh.v[k] > 0.f)) g.v[k] = 0.f;
-            a.v[k] = A.v[k] * g.v[k] + Bc.v[k] * a.v[k] + Cc.v[k];
-        }
-        stv<V>(dx + i * V, a);
-    }
-}
-// bn_bwd_apply_remask_kernel on dz = dy * sigmoid(gate) + dmean * inv_hw (SeBnBwdRemaskF): dz itself is never written
-template <int V>
-__global__ void __launch_bounds__(256) bn_bwd_apply_remask_se_kernel(const float* __restrict__ dy, const float* __restrict__ gate, const float* __restrict__ dmean,
-                                                                     const float* __restrict__ x, const float* __restrict__ fcoef, const float* __restrict__ coef,
-                                                                     float* __restrict__ dx, long nvec, int C, long vec_per_b, float inv_hw) {
-    const int cv = C / V;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % cv) * V;
-        const long bc = (i / vec_per_b) * C + c;
-        vecf<V> g = ldv<V>(dy + i * V), a = ldv<V>(x + i * V), A = ldv<V>(coef + c), Bc = ldv<V>(coef + C + c), Cc = ldv<V>(coef + 2 * C + c);
-        vecf<V> sc = ldv<V>(fcoef + c), sh = ldv<V>(fcoef + C + c), gt = ldv<V>(gate + bc), dm = ldv<V>(dmean + bc);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            float gi = g.v[k] * (1.f / (1.f + expf(-gt.v[k]))) + dm.v[k] * inv_hw;
-            if (!(a.v[k] * sc.v[k] + sh.v[k] > 0.f)) gi = 0.f;
-            a.v[k] = A.v[k] * gi + Bc.v[k] * a.v[k] + Cc.v[k];
-        }
-        stv<V>(dx + i * V, a);
-    }
-}
-// dx (+)= dy * sigmoid(gate[b][c]) + dmean[b][c] * inv_hw      (either term optional)
-template <int V>
-__global__ void __launch_bounds__(256) se_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ gate, const float* __restrict__ dmean,
-                                                           float* __restrict__ dx, long nvec, int C, long vec_per_b, float inv_hw, int accumulate) {
-    const int cv = C / V;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % cv) * V;
-        const long b = i / vec_per_b;
-        vecf<V> o;
-#pragma unroll
-        for (int k = 0; k < V; ++k) o.v[k] = 0.f;
-        if (dy) {
-            vecf<V> a = ldv<V>(dy + i * V), g = ldv<V>(gate + b * C + c);
-#pragma unroll
-            for (int k = 0; k < V; ++k) o.v[k] = a.v[k] * (1.f / (1.f + expf(-g.v[k])));
-        }
-        if (dmean) {
-            vecf<V> m = ldv<V>(dmean + b * C + c);
-#pragma unroll
-            for (int k = 0; k < V; ++k) o.v[k] += m.v[k] * inv_hw;
-        }
-        if (accumulate) { vecf<V> p = ldv<V>(dx + i * V);
-#pragma unroll
-            for (int k = 0; k < V; ++k) o.v[k] += p.v[k]; }
-        stv<V>(dx + i * V, o);
+        stv<V>(dx + o, bn_bwd_dx(g, a, A, Bc, Cc));
     }
 }
 
@@ -708,8 +655,8 @@ __global__ void __launch_bounds__(256) colsum_multi_kernel(MultiSum d, int rows)
 // launch per operand costs more than the packed GEMMs gain (measured in round 4), so the four element-wise passes that produce those operands
 // write the copies themselves: BatchNorm apply (+ shortcut + ReLU: the block output = the next block's conv1 input), BatchNorm apply + ReLU + SE scale
 // (conv3's input), and the two BatchNorm backward applies (the gradients entering conv3 / conv1).  One 64 x 64 tile per block: the value of an element
-// is computed ONCE by the functor (the expression of the fp32 kernel it replaces, so the copy is bitwise cast16 of that kernel's output), stored as
-// fp32 where something still reads it, packed row-major, and transposed through LDS (rows zero-padded to a multiple of 8) - cast16.cpp's tile.
+// is computed ONCE by the functor (the SAME functor type ew_kernel runs for the fp32 pass it replaces, so the copy is bitwise cast16 of that pass's output),
+// stored as fp32 where something still reads it, packed row-major, and transposed through LDS (rows zero-padded to a multiple of 8) - cast16.cpp's tile.
 constexpr int T16S = 64, T16P = T16S + 8;
 template <class F>
 __global__ void __launch_bounds__(256) tile16_kernel(F f, int rows, int C, uint16_t* __restrict__ y, uint16_t* __restrict__ yt, long ldyt, int f16) {
@@ -720,7 +667,12 @@ __global__ void __launch_bounds__(256) tile16_kernel(F f, int rows, int C, uint1
         const int row = it * 16 + (tid >> 4), r = r0 + row, c = c0 + c4;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         const bool in = r < rows && c < C;          // C % 4 == 0: a float4 never straddles the edge
-        if (in) f(r, c, v);
+        if (in) {
+            vecf<4> t;
+            f((long)r * C + c, r, c, t);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = t.v[e];
+        }
         uint16_t h[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) h[e] = cvt16_bits(v[e], f16 != 0);
@@ -739,64 +691,6 @@ __global__ void __launch_bounds__(256) tile16_kernel(F f, int rows, int C, uint1
         if (c0 + col < C && r0 + rc < rows8) *reinterpret_cast<float4*>(yt + (long)(c0 + col) * ldyt + r0 + rc) = *reinterpret_cast<const float4*>(T + col * T16P + rc);
     }
 }
-struct BnApply16F {          // bn_apply_kernel: y = x sc + sh (+ res) (relu); y32 (may be NULL) keeps the fp32 result
-    const float* x; const float* coef; const float* res; float* y32; int C; int relu;
-    __device__ __forceinline__ void operator()(int r, int c, float (&v)[4]) const {
-        const long o = (long)r * C + c;
-        const vecf<4> a = ldv<4>(x + o), s = ldv<4>(coef + c), t = ldv<4>(coef + C + c);
-        vecf<4> rr;
-        if (res) rr = ldv<4>(res + o);
-        vecf<4> out;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float w = a.v[k] * s.v[k] + t.v[k];
-            if (res) w += rr.v[k];
-            if (relu) w = fmaxf(w, 0.f);
-            out.v[k] = v[k] = w;
-        }
-        if (y32) stv<4>(y32 + o, out);
-    }
-};
-struct SeScaleBn16F {        // se_scale_bn_kernel: y = max(x sc + sh, 0) * sigmoid(gate[b][c]), b = row / HW
-    const float* x; const float* coef; const float* gate; int C; int HW;
-    __device__ __forceinline__ void operator()(int r, int c, float (&v)[4]) const {
-        const long o = (long)r * C + c;
-        const vecf<4> a = ldv<4>(x + o), g = ldv<4>(gate + (long)(r / HW) * C + c), sc = ldv<4>(coef + c), sh = ldv<4>(coef + C + c);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = fmaxf(a.v[k] * sc.v[k] + sh.v[k], 0.f) * (1.f / (1.f + expf(-g.v[k])));
-    }
-};
-struct BnBwdApply16F {       // bn_bwd_apply_kernel: g = dz [z > 0] (-> dres), dx = A g + Bc x + Cc; dx32 (may be NULL) keeps the fp32 result
-    const float* dz; const float* z; const float* x; const float* coef; float* dx32; float* dres; int C;
-    __device__ __forceinline__ void operator()(int r, int c, float (&v)[4]) const {
-        const long o = (long)r * C + c;
-        vecf<4> g = ldv<4>(dz + o);
-        const vecf<4> a = ldv<4>(x + o), A = ldv<4>(coef + c), Bc = ldv<4>(coef + C + c), Cc = ldv<4>(coef + 2 * C + c);
-        if (z) { const vecf<4> zz = ldv<4>(z + o);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (!(zz.v[k] > 0.f)) g.v[k] = 0.f; }
-        if (dres) stv<4>(dres + o, g);
-        vecf<4> out;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) out.v[k] = v[k] = A.v[k] * g.v[k] + Bc.v[k] * a.v[k] + Cc.v[k];
-        if (dx32) stv<4>(dx32 + o, out);
-    }
-};
-struct BnBwdRemask16F {      // bn_bwd_apply_remask_kernel: the ReLU mask recomputed from x and the forward (scale | shift)
-    const float* dz; const float* x; const float* fcoef; const float* coef; float* dx32; int C;
-    __device__ __forceinline__ void operator()(int r, int c, float (&v)[4]) const {
-        const long o = (long)r * C + c;
-        vecf<4> g = ldv<4>(dz + o);
-        const vecf<4> a = ldv<4>(x + o), A = ldv<4>(coef + c), Bc = ldv<4>(coef + C + c), Cc = ldv<4>(coef + 2 * C + c), sc = ldv<4>(fcoef + c), sh = ldv<4>(fcoef + C + c);
-        vecf<4> out;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (!(a.v[k] * sc.v[k] + sh.v[k] > 0.f)) g.v[k] = 0.f;
-            out.v[k] = v[k] = A.v[k] * g.v[k] + Bc.v[k] * a.v[k] + Cc.v[k];
-        }
-        if (dx32) stv<4>(dx32 + o, out);
-    }
-};
 template <class F>
 inline void launch_tile16(const F& f, int rows, int C, void* y16, void* y16t, int ldyt, int dtype, void* stream) {
     TF_LAUNCH(tile16_kernel<F>, dim3(cdiv(C, T16S), cdiv(rows, T16S)), dim3(256), stream, f, rows, C, (uint16_t*)y16, (uint16_t*)y16t, (long)ldyt, dtype == 2 ? 1 : 0);
@@ -804,6 +698,29 @@ inline void launch_tile16(const F& f, int rows, int C, void* y16, void* y16t, in
 inline bool tile16_ok(int rows, int C, const void* y16, const void* y16t, int ldyt, int dtype) {
     return rows > 0 && C > 0 && C % 4 == 0 && (dtype == 1 || dtype == 2) && (y16 || y16t) && (!y16 || (((uintptr_t)y16) & 7) == 0) &&
            (!y16t || (aligned16(y16t) && ldyt % 8 == 0 && ldyt >= ((rows + 7) & ~7)));
+}
+// the <4> / <1> dispatch of every ew_kernel launch; n = elements.  (The launch's TF_ABLATE name is this function's, which spells out the functor type.)
+template <class F>
+inline void launch_ew(const F& f, bool v4, long n, void* stream) {
+    if (v4) TF_LAUNCH_AS(__PRETTY_FUNCTION__, (ew_kernel<4, F>), dim3(ew_blocks(n / 4)), dim3(256), stream, f, n / 4);
+    else TF_LAUNCH_AS(__PRETTY_FUNCTION__, (ew_kernel<1, F>), dim3(ew_blocks(n)), dim3(256), stream, f, n);
+}
+// y = x sc + sh (+ res) (relu) with coef = [sc | sh]: the apply pass of the BatchNorm forwards
+inline void launch_bn_apply(const float* x, const float* coef, const float* res, int relu, float* y, int rows, int C, void* stream) {
+    const bool v4 = (C % 4 == 0) && aligned16(x) && aligned16(y) && (!res || aligned16(res));
+    launch_ew(BnApplyF{x, coef, res, y, C, relu}, v4, (long)rows * C, stream);
+}
+// The first two launches of a BatchNorm backward on the chunk-partials path (no atomics): (sum g | sum g xhat) per row chunk over the gradient source
+// ``grad``, then bn_bwd_finalize_kernel - dgamma / dbeta accumulated, the apply pass's [A | Bc | Cc] left in the workspace's upper half (returned).
+template <class G>
+inline const float* bn_bwd_sums(const G& grad, bool allow_vec, const float* x, int rows, int C, const float* gamma, const float* save_mean,
+                                const float* save_invstd, float* dgamma, float* dbeta, float* ws, void* stream) {
+    float* coef = ws + kWsFloats / 2;
+    const RedPlan p = plan_reduce(rows, C, 1, 2, allow_vec);
+    launch_reduce<2>(p, BnBwdF<G>{grad, x, save_mean, save_invstd, C}, rows, C, 1, ws, stream);
+    TF_LAUNCH(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, gamma, save_mean, save_invstd, dgamma, dbeta, coef, C, p.nchunks,
+              (float)rows);
+    return coef;
 }
 }  // namespace
 
@@ -821,9 +738,8 @@ extern "C" int tf_bn_fwd_f32(const float* x, int rows, int C, const float* gamma
         TF_REQUIRE(save_mean && save_invstd, "tf_bn_fwd_f32: training needs save_mean/save_invstd");
         const bool v4ok = aligned16(x) && aligned16(y) && (!res || aligned16(res));
         RedPlan p = plan_reduce(rows, C, 1, 2, v4ok);
-        BnStatF<4> f4{x, x, C};
-        BnStatF<1> f1{x, x, C};
-        launch_reduce<2>(p, f4, f1, rows, C, 1, zacc, stream, 2, 1.f);
+        const BnStatF f{x, x, C};
+        launch_reduce<2>(p, f, rows, C, 1, zacc, stream, 2, 1.f);
         dim3 grid(p.coltiles, p.nchunks);
         if (p.V == 4) TF_LAUNCH(bn_apply_cols_kernel<4>, grid, dim3(256), stream, x, (const float*)zacc, gamma, beta, running_mean, running_var, save_mean,
                                 save_invstd, res, y, rows, C, p.CTV, p.rows_per_chunk, (float)rows, momentum, eps, relu);
@@ -834,9 +750,8 @@ extern "C" int tf_bn_fwd_f32(const float* x, int rows, int C, const float* gamma
     if (training) {
         TF_REQUIRE(save_mean && save_invstd, "tf_bn_fwd_f32: training needs save_mean/save_invstd");
         RedPlan p = plan_reduce(rows, C, 1, 2);
-        BnStatF<4> f4{x, x, C};  // shift K = first row of x
-        BnStatF<1> f1{x, x, C};
-        launch_reduce<2>(p, f4, f1, rows, C, 1, ws, stream);
+        const BnStatF f{x, x, C};  // shift K = first row of x
+        launch_reduce<2>(p, f, rows, C, 1, ws, stream);
         TF_LAUNCH(bn_fwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, x, gamma, beta, running_mean, running_var,
                   save_mean, save_invstd, coef, C, p.nchunks, (float)rows, momentum, eps);
     } else {
@@ -844,10 +759,7 @@ extern "C" int tf_bn_fwd_f32(const float* x, int rows, int C, const float* gamma
         TF_LAUNCH(bn_eval_coef_kernel, dim3(cdiv(C, 256)), dim3(256), stream, gamma, beta, (const float*)running_mean, (const float*)running_var,
                   coef, C, eps);
     }
-    const bool v4 = (C % 4 == 0) && aligned16(x) && aligned16(y) && (!res || aligned16(res));
-    const long n = (long)rows * C;
-    if (v4) TF_LAUNCH(bn_apply_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, x, (const float*)coef, res, y, n / 4, C, relu);
-    else TF_LAUNCH(bn_apply_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, x, (const float*)coef, res, y, n, C, relu);
+    launch_bn_apply(x, coef, res, relu, y, rows, C, stream);
     return launch_status("tf_bn_fwd_f32");
 }
 
@@ -859,10 +771,7 @@ extern "C" int tf_bn_fwd_parts_f32(const float* x, int rows, int C, const float*
     TF_REQUIRE(x && parts && nparts > 0 && nparts <= 16384 && gamma && beta && y && save_mean && save_invstd && ws && rows > 0 && C > 0, "tf_bn_fwd_parts_f32: bad arguments");
     float* coef = ws + kWsFloats / 2;
     launch_finalize_parts(parts, nparts, gamma, beta, running_mean, running_var, save_mean, save_invstd, coef, C, (float)rows, momentum, eps, stream);
-    const bool v4 = (C % 4 == 0) && aligned16(x) && aligned16(y) && (!res || aligned16(res));
-    const long n = (long)rows * C;
-    if (v4) TF_LAUNCH(bn_apply_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, x, (const float*)coef, res, y, n / 4, C, relu);
-    else TF_LAUNCH(bn_apply_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, x, (const float*)coef, res, y, n, C, relu);
+    launch_bn_apply(x, coef, res, relu, y, rows, C, stream);
     return launch_status("tf_bn_fwd_parts_f32");
 }
 
@@ -871,13 +780,11 @@ extern "C" int tf_bn_fwd_parts_f32(const float* x, int rows, int C, const float*
 extern "C" int tf_bn_bwd_f32(const float* dz, const float* z, const float* x, int rows, int C, const float* gamma, const float* save_mean,
                              const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, float* ws, float* zacc, void* stream) {
     TF_REQUIRE(dz && x && gamma && save_mean && save_invstd && dx && ws && rows > 0 && C > 0, "tf_bn_bwd_f32: bad arguments");
-    float* coef = ws + kWsFloats / 2;
-    const bool v4ok = aligned16(dz) && aligned16(x) && aligned16(dx) && (!z || aligned16(z)) && (!dres || aligned16(dres));
-    RedPlan p = plan_reduce(rows, C, 1, 2, zacc ? v4ok : true);
-    BnBwdF<4> f4{dz, z, x, save_mean, save_invstd, C};
-    BnBwdF<1> f1{dz, z, x, save_mean, save_invstd, C};
+    const GradZ grad{dz, z};
     if (zacc) {
-        launch_reduce<2>(p, f4, f1, rows, C, 1, zacc, stream, 2, 1.f);
+        const bool v4ok = aligned16(dz) && aligned16(x) && aligned16(dx) && (!z || aligned16(z)) && (!dres || aligned16(dres));
+        RedPlan p = plan_reduce(rows, C, 1, 2, v4ok);
+        launch_reduce<2>(p, BnBwdF<GradZ>{grad, x, save_mean, save_invstd, C}, rows, C, 1, zacc, stream, 2, 1.f);
         dim3 grid(p.coltiles, p.nchunks);
         if (p.V == 4) TF_LAUNCH(bn_bwd_apply_cols_kernel<4>, grid, dim3(256), stream, dz, z, x, (const float*)zacc, gamma, save_mean, save_invstd, dgamma,
                                 dbeta, dx, dres, rows, C, p.CTV, p.rows_per_chunk, (float)rows);
@@ -885,13 +792,9 @@ extern "C" int tf_bn_bwd_f32(const float* dz, const float* z, const float* x, in
                        dres, rows, C, p.CTV, p.rows_per_chunk, (float)rows);
         return launch_status("tf_bn_bwd_f32");
     }
-    launch_reduce<2>(p, f4, f1, rows, C, 1, ws, stream);
-    TF_LAUNCH(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, gamma, save_mean, save_invstd, dgamma, dbeta, coef,
-              C, p.nchunks, (float)rows);
+    const float* coef = bn_bwd_sums(grad, true, x, rows, C, gamma, save_mean, save_invstd, dgamma, dbeta, ws, stream);
     const bool v4 = (C % 4 == 0) && aligned16(dz) && aligned16(x) && aligned16(dx) && (!z || aligned16(z)) && (!dres || aligned16(dres));
-    const long n = (long)rows * C;
-    if (v4) TF_LAUNCH(bn_bwd_apply_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, dz, z, x, (const float*)coef, dx, dres, n / 4, C);
-    else TF_LAUNCH(bn_bwd_apply_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, dz, z, x, (const float*)coef, dx, dres, n, C);
+    launch_ew(BnBwdApplyF<GradZ>{grad, x, coef, dx, dres, C}, v4, (long)rows * C, stream);
     return launch_status("tf_bn_bwd_f32");
 }
 
@@ -901,14 +804,13 @@ extern "C" int tf_colsum_f32(const float* x, const float* mask, int nseg, int ro
                              float* ws, void* stream) {
     TF_REQUIRE(x && out && ws && nseg > 0 && rows_per_seg > 0 && C > 0, "tf_colsum_f32: bad arguments");
     RedPlan p = plan_reduce(rows_per_seg, C, nseg, 1, aligned16(x) && (!mask || aligned16(mask)));
-    MaskSumF<4> f4{x, mask, C};
-    MaskSumF<1> f1{x, mask, C};
+    const MaskSumF f{x, mask, C};
     static const bool atomic_colsum = [] { const char* e = getenv("TF_ATOMIC_COLSUM"); return e ? e[0] != '0' : false; }();   // measured slower on the MI355X (165.4 vs 167.1 samples/s): opt-in
     if (accumulate && atomic_colsum) {   // += : the blocks add straight into the destination with fp32 atomics - one launch, no partials, no finalize
-        launch_reduce<1>(p, f4, f1, rows_per_seg, C, nseg, out, stream, 1, scale);
+        launch_reduce<1>(p, f, rows_per_seg, C, nseg, out, stream, 1, scale);
         return launch_status("tf_colsum_f32");
     }
-    launch_reduce<1>(p, f4, f1, rows_per_seg, C, nseg, ws, stream);
+    launch_reduce<1>(p, f, rows_per_seg, C, nseg, ws, stream);
     TF_LAUNCH(colsum_finalize_kernel, dim3(cdiv((long)nseg * C, 4)), dim3(256), stream, (const float*)ws, out, C, p.nchunks, nseg, scale, accumulate);
     return launch_status("tf_colsum_f32");
 }
@@ -916,20 +818,16 @@ extern "C" int tf_colsum_f32(const float* x, const float* mask, int nseg, int ro
 // Squeeze-Excite scale (timm SEModule): y = x * sigmoid(gate[b][c]); x: (B, HW, C), gate: (B, C) pre-sigmoid.
 extern "C" int tf_se_scale_fwd_f32(const float* x, const float* gate, float* y, int B, int HW, int C, void* stream) {
     TF_REQUIRE(x && gate && y && B > 0 && HW > 0 && C > 0, "tf_se_scale_fwd_f32: bad arguments");
-    const long n = (long)B * HW * C;
-    if (C % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(gate))
-        TF_LAUNCH(se_scale_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, x, gate, y, n / 4, C, (long)HW * C / 4);
-    else
-        TF_LAUNCH(se_scale_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, x, gate, y, n, C, (long)HW * C);
+    const bool v4 = C % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(gate);
+    launch_ew(SeScaleF{x, gate, y, C, HW}, v4, (long)B * HW * C, stream);
     return launch_status("tf_se_scale_fwd_f32");
 }
 // dgate_pre[b][c] = (sum_hw dy * x) * s(1-s)
 extern "C" int tf_se_scale_bwd_gate_f32(const float* dy, const float* x, const float* gate, float* dgate, int B, int HW, int C, float* ws, void* stream) {
     TF_REQUIRE(dy && x && gate && dgate && ws && B > 0 && HW > 0 && C > 0, "tf_se_scale_bwd_gate_f32: bad arguments");
     RedPlan p = plan_reduce(HW, C, B, 1);
-    MulF<4> f4{dy, x, C};
-    MulF<1> f1{dy, x, C};
-    launch_reduce<1>(p, f4, f1, HW, C, B, ws, stream);
+    const MulF f{dy, x, C};
+    launch_reduce<1>(p, f, HW, C, B, ws, stream);
     TF_LAUNCH(se_bwd_finalize_kernel, dim3(cdiv((long)B * C, 4)), dim3(256), stream, (const float*)ws, gate, dgate, C, p.nchunks, B);
     return launch_status("tf_se_scale_bwd_gate_f32");
 }
@@ -938,10 +836,8 @@ extern "C" int tf_se_scale_bwd_gate_f32(const float* dy, const float* x, const f
 extern "C" int tf_se_scale_bwd_x_f32(const float* dy, const float* gate, const float* dmean, float* dx, int B, int HW, int C, int accumulate,
                                      void* stream) {
     TF_REQUIRE(dx && (dy || dmean) && (!dy || gate) && B > 0 && HW > 0 && C > 0, "tf_se_scale_bwd_x_f32: bad arguments");
-    const long n = (long)B * HW * C;
     const bool v4 = C % 4 == 0 && aligned16(dx) && (!dy || (aligned16(dy) && aligned16(gate))) && (!dmean || aligned16(dmean));
-    if (v4) TF_LAUNCH(se_bwd_apply_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, dy, gate, dmean, dx, n / 4, C, (long)HW * C / 4, 1.f / HW, accumulate);
-    else TF_LAUNCH(se_bwd_apply_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, dy, gate, dmean, dx, n, C, (long)HW * C, 1.f / HW, accumulate);
+    launch_ew(SeBwdApplyF{dy, gate, dmean, dx, C, HW, 1.f / HW, accumulate}, v4, (long)B * HW * C, stream);
     return launch_status("tf_se_scale_bwd_x_f32");
 }
 
@@ -960,9 +856,8 @@ extern "C" int tf_colsum_bnrelu_parts_f32(const float* x, const float* coef, int
     TF_REQUIRE(x && coef && ws && nchunks && nseg > 0 && rows_per_seg > 0 && C > 0, "tf_colsum_bnrelu_parts_f32: bad arguments");
     RedPlan p = plan_reduce(rows_per_seg, C, nseg, 1, aligned16(x) && aligned16(coef));
     cap_chunks(p, rows_per_seg, 8);      // the consumer sums the chunks serially: few, fat chunks (nseg x coltiles x 8 blocks still fill the GPU)
-    BnReluSumF<4> f4{x, coef, C};
-    BnReluSumF<1> f1{x, coef, C};
-    launch_reduce<1>(p, f4, f1, rows_per_seg, C, nseg, ws, stream);
+    const BnReluSumF f{x, coef, C};
+    launch_reduce<1>(p, f, rows_per_seg, C, nseg, ws, stream);
     *nchunks = p.nchunks;
     return launch_status("tf_colsum_bnrelu_parts_f32");
 }
@@ -971,36 +866,25 @@ extern "C" int tf_se_gate_grad_parts_f32(const float* dy, const float* x, const 
     TF_REQUIRE(dy && x && coef && ws && nchunks && B > 0 && HW > 0 && C > 0, "tf_se_gate_grad_parts_f32: bad arguments");
     RedPlan p = plan_reduce(HW, C, B, 1, aligned16(x) && aligned16(coef) && aligned16(dy));
     cap_chunks(p, HW, 8);
-    BnReluMulF<4> f4{dy, x, coef, C};
-    BnReluMulF<1> f1{dy, x, coef, C};
-    launch_reduce<1>(p, f4, f1, HW, C, B, ws, stream);
+    const BnReluMulF f{dy, x, coef, C};
+    launch_reduce<1>(p, f, HW, C, B, ws, stream);
     *nchunks = p.nchunks;
     return launch_status("tf_se_gate_grad_parts_f32");
 }
 extern "C" int tf_se_scale_bn_fwd_f32(const float* x, const float* coef, const float* gate, float* y, int B, int HW, int C, void* stream) {
     TF_REQUIRE(x && coef && gate && y && B > 0 && HW > 0 && C > 0, "tf_se_scale_bn_fwd_f32: bad arguments");
-    const long n = (long)B * HW * C;
-    if (C % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(gate) && aligned16(coef))
-        TF_LAUNCH(se_scale_bn_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, x, coef, gate, y, n / 4, C, (long)HW * C / 4);
-    else
-        TF_LAUNCH(se_scale_bn_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, x, coef, gate, y, n, C, (long)HW * C);
+    const bool v4 = C % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(gate) && aligned16(coef);
+    launch_ew(SeScaleBnF{x, coef, gate, y, C, HW}, v4, (long)B * HW * C, stream);
     return launch_status("tf_se_scale_bn_fwd_f32");
 }
 // BatchNorm backward behind a ReLU whose output was never stored: the mask is [x sc + sh > 0] with the forward's (scale | shift) = fcoef
 extern "C" int tf_bn_bwd_remask_f32(const float* dz, const float* x, const float* fcoef, int rows, int C, const float* gamma, const float* save_mean,
                                     const float* save_invstd, float* dx, float* dgamma, float* dbeta, float* ws, void* stream) {
     TF_REQUIRE(dz && x && fcoef && gamma && save_mean && save_invstd && dx && ws && rows > 0 && C > 0, "tf_bn_bwd_remask_f32: bad arguments");
-    float* coef = ws + kWsFloats / 2;
     const bool v4 = (C % 4 == 0) && aligned16(dz) && aligned16(x) && aligned16(dx) && aligned16(fcoef);
-    RedPlan p = plan_reduce(rows, C, 1, 2, v4);
-    BnBwdRemaskF<4> f4{dz, x, fcoef, save_mean, save_invstd, C};
-    BnBwdRemaskF<1> f1{dz, x, fcoef, save_mean, save_invstd, C};
-    launch_reduce<2>(p, f4, f1, rows, C, 1, ws, stream);
-    TF_LAUNCH(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, gamma, save_mean, save_invstd, dgamma, dbeta, coef, C, p.nchunks,
-              (float)rows);
-    const long n = (long)rows * C;
-    if (v4) TF_LAUNCH(bn_bwd_apply_remask_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, dz, x, fcoef, (const float*)coef, dx, n / 4, C);
-    else TF_LAUNCH(bn_bwd_apply_remask_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, dz, x, fcoef, (const float*)coef, dx, n, C);
+    const GradRemask grad{dz, fcoef, C};
+    const float* coef = bn_bwd_sums(grad, v4, x, rows, C, gamma, save_mean, save_invstd, dgamma, dbeta, ws, stream);
+    launch_ew(BnBwdApplyF<GradRemask>{grad, x, coef, dx, nullptr, C}, v4, (long)rows * C, stream);
     return launch_status("tf_bn_bwd_remask_f32");
 }
 
@@ -1011,18 +895,10 @@ extern "C" int tf_bn_bwd_remask_se_f32(const float* dy, const float* gate, const
                                        void* stream) {
     TF_REQUIRE(dy && gate && dmean && x && fcoef && gamma && save_mean && save_invstd && dx && ws && B > 0 && HW > 0 && C > 0, "tf_bn_bwd_remask_se_f32: bad arguments");
     const int rows = B * HW;
-    float* coef = ws + kWsFloats / 2;
     const bool v4 = (C % 4 == 0) && aligned16(dy) && aligned16(x) && aligned16(dx) && aligned16(fcoef) && aligned16(gate) && aligned16(dmean);
-    RedPlan p = plan_reduce(rows, C, 1, 2, v4);
-    const float inv_hw = 1.f / (float)HW;
-    SeBnBwdRemaskF<4> f4{dy, gate, dmean, x, fcoef, save_mean, save_invstd, C, HW, inv_hw};
-    SeBnBwdRemaskF<1> f1{dy, gate, dmean, x, fcoef, save_mean, save_invstd, C, HW, inv_hw};
-    launch_reduce<2>(p, f4, f1, rows, C, 1, ws, stream);
-    TF_LAUNCH(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, gamma, save_mean, save_invstd, dgamma, dbeta, coef, C, p.nchunks,
-              (float)rows);
-    const long n = (long)rows * C;
-    if (v4) TF_LAUNCH(bn_bwd_apply_remask_se_kernel<4>, dim3(ew_blocks(n / 4)), dim3(256), stream, dy, gate, dmean, x, fcoef, (const float*)coef, dx, n / 4, C, (long)HW * C / 4, inv_hw);
-    else TF_LAUNCH(bn_bwd_apply_remask_se_kernel<1>, dim3(ew_blocks(n)), dim3(256), stream, dy, gate, dmean, x, fcoef, (const float*)coef, dx, n, C, (long)HW * C, inv_hw);
+    const GradRemaskSe grad{dy, gate, dmean, fcoef, C, HW, 1.f / (float)HW};
+    const float* coef = bn_bwd_sums(grad, v4, x, rows, C, gamma, save_mean, save_invstd, dgamma, dbeta, ws, stream);
+    launch_ew(BnBwdApplyF<GradRemaskSe>{grad, x, coef, dx, nullptr, C}, v4, (long)rows * C, stream);
     return launch_status("tf_bn_bwd_remask_se_f32");
 }
 
@@ -1030,9 +906,8 @@ extern "C" int tf_bn_bwd_remask_se_f32(const float* dy, const float* gate, const
 extern "C" int tf_colsum_mul_f32(const float* a, const float* b, int rows, int C, float* out, int accumulate, float* ws, void* stream) {
     TF_REQUIRE(a && b && out && ws && rows > 0 && C > 0, "tf_colsum_mul_f32: bad arguments");
     RedPlan p = plan_reduce(rows, C, 1, 1, aligned16(a) && aligned16(b));
-    MulF<4> f4{a, b, C};
-    MulF<1> f1{a, b, C};
-    launch_reduce<1>(p, f4, f1, rows, C, 1, ws, stream);
+    const MulF f{a, b, C};
+    launch_reduce<1>(p, f, rows, C, 1, ws, stream);
     TF_LAUNCH(colsum_finalize_kernel, dim3(cdiv((long)C, 4)), dim3(256), stream, (const float*)ws, out, C, p.nchunks, 1, 1.f, accumulate);
     return launch_status("tf_colsum_mul_f32");
 }
@@ -1066,14 +941,14 @@ extern "C" int tf_bn_apply16_f32(const float* x, const float* coef, const float*
                                  int dtype, void* stream) {
     TF_REQUIRE(x && coef && tile16_ok(rows, C, y16, y16t, ldyt, dtype) && aligned16(x) && aligned16(coef) && (!res || aligned16(res)) && (!y32 || aligned16(y32)),
                "tf_bn_apply16_f32: needs C %% 4 == 0, 16-byte aligned tensors, dtype 1 / 2, ldyt %% 8 == 0 and >= rows rounded up to 8");
-    launch_tile16(BnApply16F{x, coef, res, y32, C, relu}, rows, C, y16, y16t, ldyt, dtype, stream);
+    launch_tile16(BnApplyF{x, coef, res, y32, C, relu}, rows, C, y16, y16t, ldyt, dtype, stream);
     return launch_status("tf_bn_apply16_f32");
 }
 extern "C" int tf_se_scale_bn16_f32(const float* x, const float* coef, const float* gate, int B, int HW, int C, void* y16, void* y16t, int ldyt, int dtype,
                                     void* stream) {
     TF_REQUIRE(x && coef && gate && B > 0 && HW > 0 && tile16_ok(B * HW, C, y16, y16t, ldyt, dtype) && aligned16(x) && aligned16(coef) && aligned16(gate),
                "tf_se_scale_bn16_f32: needs C %% 4 == 0, 16-byte aligned tensors, dtype 1 / 2, ldyt %% 8 == 0 and >= rows rounded up to 8");
-    launch_tile16(SeScaleBn16F{x, coef, gate, C, HW}, B * HW, C, y16, y16t, ldyt, dtype, stream);
+    launch_tile16(SeScaleBnF{x, coef, gate, nullptr, C, HW}, B * HW, C, y16, y16t, ldyt, dtype, stream);
     return launch_status("tf_se_scale_bn16_f32");
 }
 // tf_bn_bwd_f32 (chunk partials + finalize, no atomics) whose apply pass writes dx as 16-bit copies (+ fp32 dx32 when not NULL, + dres)
@@ -1083,14 +958,9 @@ extern "C" int tf_bn_bwd16_f32(const float* dz, const float* z, const float* x, 
     TF_REQUIRE(dz && x && gamma && save_mean && save_invstd && ws && tile16_ok(rows, C, dx16, dx16t, ldyt, dtype) && aligned16(dz) && aligned16(x) &&
                (!z || aligned16(z)) && (!dres || aligned16(dres)) && (!dx32 || aligned16(dx32)),
                "tf_bn_bwd16_f32: needs C %% 4 == 0, 16-byte aligned tensors, dtype 1 / 2, ldyt %% 8 == 0 and >= rows rounded up to 8");
-    float* coef = ws + kWsFloats / 2;
-    RedPlan p = plan_reduce(rows, C, 1, 2, true);
-    BnBwdF<4> f4{dz, z, x, save_mean, save_invstd, C};
-    BnBwdF<1> f1{dz, z, x, save_mean, save_invstd, C};
-    launch_reduce<2>(p, f4, f1, rows, C, 1, ws, stream);
-    TF_LAUNCH(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, gamma, save_mean, save_invstd, dgamma, dbeta, coef, C, p.nchunks,
-              (float)rows);
-    launch_tile16(BnBwdApply16F{dz, z, x, (const float*)coef, dx32, dres, C}, rows, C, dx16, dx16t, ldyt, dtype, stream);
+    const GradZ grad{dz, z};
+    const float* coef = bn_bwd_sums(grad, true, x, rows, C, gamma, save_mean, save_invstd, dgamma, dbeta, ws, stream);
+    launch_tile16(BnBwdApplyF<GradZ>{grad, x, coef, dx32, dres, C}, rows, C, dx16, dx16t, ldyt, dtype, stream);
     return launch_status("tf_bn_bwd16_f32");
 }
 extern "C" int tf_bn_bwd_remask16_f32(const float* dz, const float* x, const float* fcoef, int rows, int C, const float* gamma, const float* save_mean,
@@ -1099,13 +969,8 @@ extern "C" int tf_bn_bwd_remask16_f32(const float* dz, const float* x, const flo
     TF_REQUIRE(dz && x && fcoef && gamma && save_mean && save_invstd && ws && tile16_ok(rows, C, dx16, dx16t, ldyt, dtype) && aligned16(dz) && aligned16(x) &&
                aligned16(fcoef) && (!dx32 || aligned16(dx32)),
                "tf_bn_bwd_remask16_f32: needs C %% 4 == 0, 16-byte aligned tensors, dtype 1 / 2, ldyt %% 8 == 0 and >= rows rounded up to 8");
-    float* coef = ws + kWsFloats / 2;
-    RedPlan p = plan_reduce(rows, C, 1, 2, true);
-    BnBwdRemaskF<4> f4{dz, x, fcoef, save_mean, save_invstd, C};
-    BnBwdRemaskF<1> f1{dz, x, fcoef, save_mean, save_invstd, C};
-    launch_reduce<2>(p, f4, f1, rows, C, 1, ws, stream);
-    TF_LAUNCH(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, gamma, save_mean, save_invstd, dgamma, dbeta, coef, C, p.nchunks,
-              (float)rows);
-    launch_tile16(BnBwdRemask16F{dz, x, fcoef, (const float*)coef, dx32, C}, rows, C, dx16, dx16t, ldyt, dtype, stream);
+    const GradRemask grad{dz, fcoef, C};
+    const float* coef = bn_bwd_sums(grad, true, x, rows, C, gamma, save_mean, save_invstd, dgamma, dbeta, ws, stream);
+    launch_tile16(BnBwdApplyF<GradRemask>{grad, x, coef, dx32, nullptr, C}, rows, C, dx16, dx16t, ldyt, dtype, stream);
     return launch_status("tf_bn_bwd_remask16_f32");
 }

@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(256) se_excite_bwd2_kernel(const float* __rest
                 for (; j + 3 < nch; j += 4) { v += p[(long)j * C]; v1 += p[(long)(j + 1) * C]; v2 += p[(long)(j + 2) * C]; v3 += p[(long)(j + 3) * C]; }
                 for (; j < nch; ++j) v += p[(long)j * C];
                 v = (v + v1) + (v2 + v3);
-                const float sg = 1.f / (1.f + expf(-gate[(long)b * C + n0 + r]));
+                const float sg = sigmoidf_(gate[(long)b * C + n0 + r]);
                 v *= sg * (1.f - sg);
             } else {
                 v = dgate[(long)b * C + n0 + r];

@@ -10,16 +10,16 @@ void set_error(const char* fmt, ...);  // api.cpp
 bool ablated(const char* kernel);      // api.cpp: TF_ABLATE=substr[,substr...] turns the matching kernels' launches into no-ops (timing diagnosis only)
 
 #ifdef TF_EMU
-#define TF_LAUNCH(kern, grid, block, stream, ...)                         \
+#define TF_LAUNCH_AS(name, kern, grid, block, stream, ...)               \
     do {                                                                    \
         (void)(stream);                                                     \
         emu::launch((grid), (block), [=]() { kern(__VA_ARGS__); });         \
     } while (0)
 inline int launch_status(const char*) { return 0; }
 #else
-#define TF_LAUNCH(kern, grid, block, stream, ...)                                                        \
+#define TF_LAUNCH_AS(name, kern, grid, block, stream, ...)                                              \
     do {                                                                                                   \
-        static const bool tf_ablated_ = tf::ablated(#kern);                                              \
+        static const bool tf_ablated_ = tf::ablated(name);                                               \
         if (!tf_ablated_) hipLaunchKernelGGL(kern, (grid), (block), 0, (hipStream_t)(stream), __VA_ARGS__); \
     } while (0)
 inline int launch_status(const char* what) {
@@ -31,6 +31,9 @@ inline int launch_status(const char* what) {
     return 0;
 }
 #endif
+
+// TF_ABLATE matches the kernel's name as the launch site spells it; a launch helper that is a template over functors passes a name that carries them
+#define TF_LAUNCH(kern, ...) TF_LAUNCH_AS(#kern, kern, __VA_ARGS__)
 
 #define TF_REQUIRE(cond, ...)            \
     do {                                 \

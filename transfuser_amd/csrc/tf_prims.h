@@ -348,6 +348,14 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return t;
 }
 
+// Per-element expressions that several kernels must evaluate to the SAME BITS (a ReLU mask recomputed from x sc + sh by a backward pass, a
+// 16-bit copy of an fp32 output, a gate's sigmoid in the forward and the backward): every kernel calls these, none writes them out.
+// bn_affine is a multiply, then an add - the build sets -ffp-contract=off, so it is never fused into an fma.
+__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
+__device__ __forceinline__ float bn_affine(float x, float sc, float sh) { return x * sc + sh; }
+__device__ __forceinline__ float bn_relu(float x, float sc, float sh) { return fmaxf(bn_affine(x, sc, sh), 0.f); }
+__device__ __forceinline__ float relu_mask(float g, float v) { return !(v > 0.f) ? 0.f : g; }      // g * [v > 0]: a NaN v masks
+
 // Counter-based RNG for dropout (our own stream: torch's Philox sequence is not reproduced;
 // parity tests run with p = 0).  One 32-bit hash per element, keyed by (seed, site, index).
 __device__ __forceinline__ uint32_t hash32(uint32_t x) {
