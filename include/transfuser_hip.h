@@ -35,6 +35,23 @@ long tf_streamk_launches(void);
  * eligible (alignment, N % 4, atomic mode, tiling) silently takes the 4-byte epilogue and leaves the counter alone. */
 int tf_gemm_epi16(int on);
 long tf_gemm_epi16_launches(void);
+/* Deterministic mode (the counterpart of torch.use_deterministic_algorithms, which the reference leaves off: train.py:115 only turns on
+ * cudnn.benchmark).  Process-wide, read on the host at launch time like tf_set_precision - so a captured graph keeps the forms it was
+ * captured with.  On: every reduction that by default ends in fp32 atomics (the k-split weight gradients of the MFMA engine, the grouped 3x3
+ * weight gradient, LayerNorm dgamma / dbeta, the SE excitation backward, the small-M input gradient, the skinny weight gradient, the opt-in
+ * atomic BatchNorm / column sums) takes a fixed-order form whose result is a pure function of its inputs and the GEMM plan; an entry without
+ * such a form returns an error that names this flag instead of running atomics (tf_dwconv7_wgrad_f32; tf_layernorm_bwd_f32 /
+ * tf_layernorm_bwd_drop_f32 when asked for dgamma / dbeta: use tf_layernorm_bwd_dw_f32).  Scratch for these forms is the caller's, per call:
+ * tf_gemm_desc.splitk_ws (tf_gemm_splitk_ws_floats), tf_conv2d_wgrad_ws_f32, tf_se_excite_bwd_ws_floats, the reduction workspace.  Off
+ * (default): every launch is exactly what it was.  tf_set_deterministic returns 0; tf_get_deterministic the flag. */
+int tf_set_deterministic(int on);
+int tf_get_deterministic(void);
+/* Launches so far of kernel forms that combine partial results with float atomics (the engine's atomic k-split counts only when the launch
+ * really runs with the atomic epilogue) - tests assert that it stands still under tf_set_deterministic(1) and moves without it. */
+long tf_float_atomic_launches(void);
+/* Launches so far of the ordered slab k-split of the MFMA engine: under tf_set_deterministic(1) a plan that would split K with the atomic
+ * epilogue has slice s store its raw partial tile at splitk_ws + s * m * round_up(n, 4) and a fix-up kernel add the slices to C in slice order. */
+long tf_slab_splitk_launches(void);
 
 /* GEMM tiling plans.  The reference turns on cudnn.benchmark (train.py:115); the equivalent here: while tf_autotune(1)
  * is on (eager warm-up, NOT during graph capture - it synchronises), the first call of every distinct
@@ -69,7 +86,9 @@ int tf_plans_load(const char* path);
  *   splitk_ws / splitk_ws_floats: optional caller-owned scratch (stream-ordered with this call).  When given, GEMMs whose output has too few
  *   tiles to fill the 256 CUs (e.g. the GPT-4 [1740 x 6048] . [6048 x 1512] MLP contraction: 168 tiles of 128 x 128) may run as a
  *   deterministic TWO-PASS split-K: S k-slices write partial tiles into the scratch, a fix-up kernel sums them in slice order and applies the
- *   epilogue (alpha, bias, residual, ReLU, mask, store / +=).  Needs S * m * round_up(n, 4) floats (S <= 4); NULL disables it. */
+ *   epilogue (alpha, bias, residual, ReLU, mask, store / +=).  Needs S * m * round_up(n, 4) floats (S <= 4); NULL disables it.
+ *   Under tf_set_deterministic(1) the same scratch carries the ordered slab k-split of the accumulating calls (any S: the slice count of the
+ *   plan, lowered until S slices fit; without scratch the call runs unsplit) and the block partials of the skinny weight gradient. */
 typedef struct {
     const float* a; const float* b; float* c; const float* bias; const float* res;
     int m, n, k;
@@ -100,7 +119,7 @@ int tf_gemm_f32(const tf_gemm_desc* d, void* stream);
 /* Floats of splitk_ws this call can use: 0 unless the cached (or about-to-be-tuned) plan of the call's shape is a two-pass split-K plan, so
  * the caller only allocates scratch for the few GEMMs that want it (the reference's addmm never needs caller scratch: torch's cuBLAS
  * workspace plays this role, transfuser.py:500-507,539-541). */
-long tf_gemm_splitk_ws_floats(const tf_gemm_desc* d);
+long tf_gemm_splitk_ws_floats(const tf_gemm_desc* d);   /* under tf_set_deterministic(1): also what the ordered slab k-split / the skinny weight gradient of this call want */
 /* Pair launch: between tf_gemm_pair_begin() and tf_gemm_pair_end(stream) (same thread) up to TWO tf_gemm_f32 calls whose plan is a 64 x 64
  * register-staged tiling (batch 1, 16-byte aligned operands, no output statistics) are held back and issued by tf_gemm_pair_end: a weight
  * gradient ([tn]: a_trans && b_trans) + an input gradient ([nn]: b_trans) pair as ONE grid whose second problem's workgroups start as the first
@@ -125,6 +144,11 @@ int tf_conv2d_fwd_colstat_f32(const tf_conv_geom* g, const float* x, const float
                               void* stream);
 int tf_conv2d_dgrad_f32(const tf_conv_geom* g, const float* dy, const float* w, float* dx, int accumulate, void* stream);
 int tf_conv2d_wgrad_f32(const tf_conv_geom* g, const float* dy, const float* x, float* dw, int accumulate, void* stream);
+/* tf_conv2d_wgrad_f32 with caller-owned scratch of ws_floats floats (tf_conv2d_wgrad_ws_floats(g); 0 / NULL allowed): under
+ * tf_set_deterministic(1) the k-slices of the weight gradient go through it (ordered slab k-split) instead of fp32 atomics - without scratch
+ * the call runs unsplit.  With the flag off it is tf_conv2d_wgrad_f32 and the query returns 0. */
+int tf_conv2d_wgrad_ws_f32(const tf_conv_geom* g, const float* dy, const float* x, float* dw, int accumulate, float* ws, long ws_floats, void* stream);
+long tf_conv2d_wgrad_ws_floats(const tf_conv_geom* g);
 
 /* Direct LDS-tiled 3x3 / stride 1 / pad 1 convolutions for Cin, Cout <= 32 at large resolution (the last decoder layers,
  * transfuser.py:232-237,267-272, and their gradients): one read of the input instead of 9 im2col reads through L2.  NHWC activations,
@@ -162,7 +186,7 @@ int tf_bn_bwd_remask_se_f32(const float* dy, const float* gate, const float* dme
  * (erf) form of nn.GELU.  tf_colscale_add_f32: y = res + gamma[c] x + beta[c] (each of gamma / beta / res optional): layer scale + shortcut,
  * conv bias.  tf_colsum_mul_f32: out[c] (+)= sum_r a[r][c] b[r][c] (layer-scale gradient). */
 int tf_dwconv7_fwd_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int C, int flip, int accumulate, void* stream);
-int tf_dwconv7_wgrad_f32(const float* dy, const float* x, float* dw, float* dbias, int B, int H, int W, int C, void* stream);
+int tf_dwconv7_wgrad_f32(const float* dy, const float* x, float* dw, float* dbias, int B, int H, int W, int C, void* stream);   /* fp32 atomics over the row blocks, no fixed-order form: an error under tf_set_deterministic(1) */
 int tf_gelu_fwd_f32(const float* x, float* y, int64_t n, void* stream);
 int tf_gelu_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, void* stream);
 int tf_colscale_add_f32(const float* x, const float* gamma, const float* beta, const float* res, float* y, int64_t rows, int C, void* stream);
@@ -287,6 +311,12 @@ int tf_layernorm_bwd_f32(const float* dy, const float* x, const float* gamma, co
  * (x_mid = x + resid_drop(proj(.)), transfuser.py:543-547) without a separate dropout launch (round 5).  dropped != dx. */
 int tf_layernorm_bwd_drop_f32(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, float* dx, int dx_accumulate,
                               float* dgamma, float* dbeta, int rows, int C, float* dropped, const uint32_t* seed_dev, uint32_t site, float p, void* stream);
+/* The parameter gradients of tf_layernorm_bwd_f32 alone, in fixed summation order: dgamma[c] += sum_rows dy xhat, dbeta[c] += sum_rows dy as
+ * per-row-chunk partials in ws (the tf_workspace_bytes() reduction scratch every tf_bn_* / tf_colsum_* call takes) and a second stage that adds
+ * the chunks in chunk order - bitwise reproducible, where the default form ends every 64-row block in fp32 atomics.  Under
+ * tf_set_deterministic(1) the two entries above refuse dgamma / dbeta; call them with NULL and this entry beside them. */
+int tf_layernorm_bwd_dw_f32(const float* dy, const float* x, const float* mean, const float* rstd, float* dgamma, float* dbeta, int rows, int C, float* ws,
+                            void* stream);
 /* F.softmax over attention rows (transfuser.py:520), in place; bwd turns dP into dS in place. */
 int tf_softmax_fwd_f32(float* s, int rows, int n, int ld, void* stream);
 int tf_softmax_bwd_f32(const float* p, float* dp, int rows, int n, int ld, void* stream);
@@ -351,6 +381,10 @@ int tf_se_excite_fwd_f32(const float* s, const float* W1, const float* b1, const
                          float* gate, float* bwd_scratch /* optional (B, Cr): cleared here for tf_se_excite_bwd_f32(scratch_is_zero = 1) */, void* stream);
 int tf_se_excite_bwd_f32(const float* dgate, const float* s, const float* g1, const float* W1, const float* W2, int B, int C, int Cr, float* dW1,
                          float* db1, float* dW2, float* db2, float* ds, float* scratch, int scratch_is_zero, void* stream);
+/* Floats `scratch` of tf_se_excite_bwd_f32 / tf_se_excite_bwd_parts_f32 must hold: B * Cr, and under tf_set_deterministic(1)
+ * ceil(C / 8) * B * Cr - the fc2 pass then writes one (B, Cr) slab of dg1 per block instead of adding into one with fp32 atomics, the fc1 pass
+ * sums the slabs in block order and takes all Cr rows per column block (ds is stored, not added); scratch_is_zero is ignored in that mode. */
+long tf_se_excite_bwd_ws_floats(int B, int C, int Cr);
 
 /* ---- resampling ------------------------------------------------------------------------------ */
 

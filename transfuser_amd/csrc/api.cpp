@@ -44,6 +44,8 @@ extern "C" int tf_version(void) { return 101; }
 extern "C" long tf_streamk_launches(void) { return tf::streamk_count(0); }
 extern "C" const char* tf_last_error(void) { return tf::g_err; }
 extern "C" long tf_gemm_epi16_launches(void) { return tf::epi16_count(0); }
+extern "C" long tf_float_atomic_launches(void) { return tf::float_atomic_count(0); }
+extern "C" long tf_slab_splitk_launches(void) { return tf::slab_splitk_count(0); }
 
 // ---- GEMM plan cache / autotuner switches -----------------------------------------------------------------------
 namespace tf {
@@ -66,6 +68,13 @@ void plan_store(const char* what, int M, int N, int K, int batch, int acc, const
 bool autotune_enabled() { return g_autotune; }
 long streamk_count(int add) { static long n = 0; n += add; return n; }
 long epi16_count(int add) { static long n = 0; n += add; return n; }
+long float_atomic_count(int add) { static long n = 0; n += add; return n; }
+long slab_splitk_count(int add) { static long n = 0; n += add; return n; }
+static int g_deterministic = -1;       // -1: not set yet - TF_DETERMINISTIC in the environment gives the initial value
+bool deterministic() {
+    if (g_deterministic < 0) { const char* e = getenv("TF_DETERMINISTIC"); g_deterministic = (e && atoi(e) != 0) ? 1 : 0; }
+    return g_deterministic != 0;
+}
 static int g_epi16 = -1;
 static int epi16_from_env() { const char* e = getenv("TF_GEMM_EPI16"); return (!e || atoi(e) != 0) ? 1 : 0; }
 int gemm_epi16() { if (g_epi16 < 0) g_epi16 = epi16_from_env(); return g_epi16; }
@@ -115,6 +124,8 @@ extern "C" int tf_set_precision(int mode) {
     return 0;
 }
 extern "C" int tf_get_precision(void) { return tf::g_precision; }
+extern "C" int tf_set_deterministic(int on) { tf::g_deterministic = on != 0; return 0; }
+extern "C" int tf_get_deterministic(void) { return tf::deterministic() ? 1 : 0; }
 extern "C" int tf_autotune(int enable) { tf::g_autotune = enable != 0; return 0; }
 extern "C" int tf_plans_count(void) { std::lock_guard<std::mutex> lk(tf::g_plan_mu); return (int)tf::g_plans.size(); }
 extern "C" int tf_plans_clear(void) { std::lock_guard<std::mutex> lk(tf::g_plan_mu); tf::g_plans.clear(); return 0; }

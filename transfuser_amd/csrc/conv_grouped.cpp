@@ -9,7 +9,9 @@
 // 32 MFMA columns = the 75 % ceiling of any MFMA mapping of a 24-wide group).  Tiles are 8 x 16 or 4 x 32 pixels (picked per map
 // width: 44 -> 3 x 16, 88 -> 3 x 32, 16 / 32 / 64 exact).  dgrad = the same kernel on dY with the flipped, transposed panel.  wgrad keeps
 // 9 accumulators (one per tap, 24 x 24 used of 32 x 32) per wave with the tile's pixels as the K dimension, reduced over the block's
-// waves through LDS and over a group's blocks by a second tiny kernel (deterministic, no atomics).
+// waves through LDS.  Over a group's blocks there are two forms: the default seven-wave kernel (conv3x3_grouped_wgrad7_kernel, since round 6) adds
+// its block's panel to dW with fp32 atomics - not run-to-run reproducible; the three-wave kernel writes partial panels that a second tiny kernel
+// sums in a fixed order (no atomics) - taken with TF_GROUPED_WGRAD7=0, in the 16-bit precisions and under tf_set_deterministic(1).
 #include "tf_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -1030,7 +1032,8 @@ static int grouped_wgrad(const char* what, const float* dy, const float* x, cons
     TF_REQUIRE(g.nb >= 1, "%s: %d groups exceed the workspace", what, g.G);
     const int prec = direct_prec();
     static const int v7 = [] { const char* e = getenv("TF_GROUPED_WGRAD7"); return e ? atoi(e) : 1; }();     // A/B switch: 0 = the three-wave kernel + partial panels
-    if (prec == 0 && v7) {
+    if (prec == 0 && v7 && !deterministic()) {      // (tf_set_deterministic: the three-wave kernel + partial panels + fixed-order reduce below)
+        float_atomic_count(1);
         // seven-wave blocks (conv3x3_grouped_wgrad7_kernel), 31 KB of LDS: up to four per CU.  Every block ends with 5184 atomics on its group's dW, so a
         // block takes at least two tiles when there are enough; ~3 blocks per CU otherwise (TF_GROUPED_WGRAD7 > 1: that many blocks in all, for the lab)
         GcGeom g7 = make_geom(B, H, W, C, tw, v7 > 1 ? v7 : 768);
@@ -1092,7 +1095,8 @@ extern "C" int tf_conv3x3_grouped_s2_wgrad_f32(const float* dy, const float* x, 
     g.H = Hi; g.W = Wi;
     const int prec = direct_prec();
     static const int v7 = [] { const char* e = getenv("TF_GROUPED_WGRAD7"); return e ? atoi(e) : 1; }();
-    if (prec == 0 && v7) {      // seven-wave form (69 - 72 KB of LDS: two blocks per CU), atomically accumulated: see grouped_wgrad
+    if (prec == 0 && v7 && !deterministic()) {      // seven-wave form (69 - 72 KB of LDS: two blocks per CU), atomically accumulated: see grouped_wgrad
+        float_atomic_count(1);
         GcGeom g7 = make_geom(B, Ho, Wo, C, tw, 512);
         int tpb7 = cdiv(g7.ntiles, g7.nb);
         if (tpb7 < 2 && g7.ntiles >= 2) tpb7 = 2;

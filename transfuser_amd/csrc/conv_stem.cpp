@@ -38,8 +38,9 @@ extern "C" int tf_stem_conv_fwd_f32(const tf_conv_geom* g, const float* s0, int 
     return launch_gemm<Im2colNchwOp, true, PlainOp, true>(A, Bw, ep, M, g->Cout, K, 1, false, stream, "tf_stem_conv_fwd_f32");
 }
 
-extern "C" int tf_stem_conv_wgrad_f32(const tf_conv_geom* g, const float* dy, const float* s0, int C0, const float* s1, int C1, int normalize,
-                                      float* dw, int accumulate, void* stream) {
+// the implicit-GEMM weight gradient; (ws, ws_floats): optional caller scratch for the ordered slab k-split of the deterministic mode (launch_gemm)
+static int stem_engine_wgrad(const tf_conv_geom* g, const float* dy, const float* s0, int C0, const float* s1, int C1, int normalize, float* dw, int accumulate,
+                             float* ws, long ws_floats, void* stream) {
     if (int e = check_geom(g, "tf_stem_conv_wgrad_f32")) return e;
     TF_REQUIRE(s0 && dy && dw && g->groups == 1 && C0 + C1 == g->Cin && g->Cin <= 4 && (C1 == 0 || s1), "tf_stem_conv_wgrad_f32: bad arguments");
     const int K = g->ksize * g->ksize * g->Cin, M = g->B * g->Ho * g->Wo;
@@ -50,13 +51,22 @@ extern "C" int tf_stem_conv_wgrad_f32(const tf_conv_geom* g, const float* dy, co
     GemmEpi ep;
     ep.C = dw; ep.ldc = K; ep.ldcj = 1; ep.sc_outer = 0; ep.sc_inner = 0; ep.inner = 1; ep.bias = nullptr; ep.sbias = 0; ep.res = nullptr; ep.ldres = 0;
     ep.alpha = 1.f; ep.relu = 0; ep.mode = accumulate ? 1 : 0;
+    ep.sk_ws = (ws && aligned16(ws)) ? ws : nullptr; ep.sk_ws_floats = ep.sk_ws ? ws_floats : 0;
     return launch_gemm<PlainOp, false, Im2colNchwOp, false>(A, Bx, ep, g->Cout, K, M, 1, true, stream, "tf_stem_conv_wgrad_f32");
 }
 
+extern "C" int tf_stem_conv_wgrad_f32(const tf_conv_geom* g, const float* dy, const float* s0, int C0, const float* s1, int C1, int normalize,
+                                      float* dw, int accumulate, void* stream) {
+    return stem_engine_wgrad(g, dy, s0, C0, s1, C1, normalize, dw, accumulate, nullptr, 0, stream);
+}
+
 // The same with caller scratch for the direct kernels' partial panels (tf_stem_conv_wgrad_ws_floats() floats, 0 = the engine path is used and no
-// scratch is needed): the RegNet stems take the direct path, every other stem (7x7 ResNet, 4x4 ConvNeXt) the implicit-GEMM engine.
+// scratch is needed): the RegNet stems take the direct path, every other stem (7x7 ResNet, 4x4 ConvNeXt) the implicit-GEMM engine - which under
+// tf_set_deterministic(1) wants the scratch of its ordered slab k-split (without it the weight gradient runs unsplit).
 extern "C" long tf_stem_conv_wgrad_ws_floats(const tf_conv_geom* g, int C0, int C1) {
-    return (g && stem_direct_ok(g, C0, C1)) ? stem_direct_wgrad_ws_floats(g) : 0;
+    if (!g) return 0;
+    if (stem_direct_ok(g, C0, C1)) return stem_direct_wgrad_ws_floats(g);
+    return deterministic() ? slab_ws_floats("tf_stem_conv_wgrad_f32", g->Cout, g->ksize * g->ksize * g->Cin, g->B * g->Ho * g->Wo) : 0;
 }
 extern "C" int tf_stem_conv_wgrad_ws_f32(const tf_conv_geom* g, const float* dy, const float* s0, int C0, const float* s1, int C1, int normalize, float* dw,
                                          int accumulate, float* ws, long ws_floats, void* stream) {
@@ -65,5 +75,5 @@ extern "C" int tf_stem_conv_wgrad_ws_f32(const tf_conv_geom* g, const float* dy,
         TF_REQUIRE(s0 && dy && dw && C0 + C1 == g->Cin && (C1 == 0 || s1), "tf_stem_conv_wgrad_ws_f32: bad arguments");
         return stem_direct_wgrad(g, dy, s0, C0, s1, C1, normalize, dw, accumulate, ws, stream);
     }
-    return tf_stem_conv_wgrad_f32(g, dy, s0, C0, s1, C1, normalize, dw, accumulate, stream);
+    return stem_engine_wgrad(g, dy, s0, C0, s1, C1, normalize, dw, accumulate, ws, ws ? ws_floats : 0, stream);
 }

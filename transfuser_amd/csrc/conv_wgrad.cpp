@@ -5,7 +5,7 @@
 
 using namespace tf;
 
-extern "C" int tf_conv2d_wgrad_f32(const tf_conv_geom* g, const float* dy, const float* x, float* dw, int accumulate, void* stream) {
+static int conv2d_wgrad(const tf_conv_geom* g, const float* dy, const float* x, float* dw, int accumulate, float* ws, long ws_floats, void* stream) {
     if (int e = check_geom(g, "tf_conv2d_wgrad_f32")) return e;
     const int Cig = g->Cin / g->groups, Cog = g->Cout / g->groups, taps = g->ksize * g->ksize;
     const int Mred = g->B * g->Ho * g->Wo, Ncols = taps * Cig;
@@ -20,7 +20,9 @@ extern "C" int tf_conv2d_wgrad_f32(const tf_conv_geom* g, const float* dy, const
     GemmEpi ep;
     ep.C = dw; ep.ldc = Ncols; ep.ldcj = 1; ep.sc_outer = 0; ep.sc_inner = (long)Cog * Ncols; ep.inner = g->groups; ep.bias = nullptr; ep.sbias = 0;
     ep.res = nullptr; ep.ldres = 0; ep.alpha = 1.f; ep.relu = 0; ep.mode = accumulate ? 1 : 0;
-    if (Cog <= 32) {
+    ep.sk_ws = ws; ep.sk_ws_floats = ws ? ws_floats : 0;      // the ordered slab k-split of the deterministic mode (launch_gemm); unused otherwise
+    // (deterministic mode, one group: the slab split needs a row-major output, so the unswapped orientation is kept; grouped calls run unsplit either way)
+    if (Cog <= 32 && !(deterministic() && accumulate && g->groups == 1)) {
         // few output channels per group (RegNet group width 24, decoder / head tails with 32, 7, 1): compute dW^T -
         // rows = (tap, ci), cols = co - so Cog sits in a 32-wide column tile instead of a 128-row tile.
         ep.ldc = 1; ep.ldcj = Ncols;
@@ -29,3 +31,15 @@ extern "C" int tf_conv2d_wgrad_f32(const tf_conv_geom* g, const float* dy, const
     return launch_gemm<PlainOp, false, Im2colOp, false>(A, Bx, ep, Cog, Ncols, Mred, g->groups, true, stream, "tf_conv2d_wgrad_f32");
 }
 
+extern "C" int tf_conv2d_wgrad_f32(const tf_conv_geom* g, const float* dy, const float* x, float* dw, int accumulate, void* stream) {
+    return conv2d_wgrad(g, dy, x, dw, accumulate, nullptr, 0, stream);
+}
+// the same with caller scratch for the ordered slab k-split (tf_set_deterministic); tf_conv2d_wgrad_ws_floats: what that split wants for this geometry
+extern "C" int tf_conv2d_wgrad_ws_f32(const tf_conv_geom* g, const float* dy, const float* x, float* dw, int accumulate, float* ws, long ws_floats, void* stream) {
+    TF_REQUIRE(ws_floats >= 0 && (!ws || aligned16(ws)), "tf_conv2d_wgrad_ws_f32: ws must be 16-byte aligned");
+    return conv2d_wgrad(g, dy, x, dw, accumulate, ws, ws_floats, stream);
+}
+extern "C" long tf_conv2d_wgrad_ws_floats(const tf_conv_geom* g) {
+    if (!g || !deterministic() || g->groups != 1 || check_geom(g, "tf_conv2d_wgrad_ws_floats")) return 0;
+    return slab_ws_floats("tf_conv2d_wgrad_f32", g->Cout, g->ksize * g->ksize * g->Cin, g->B * g->Ho * g->Wo);
+}

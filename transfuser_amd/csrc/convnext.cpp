@@ -146,6 +146,8 @@ extern "C" int tf_dwconv7_fwd_f32(const float* x, const float* w, const float* b
 }
 extern "C" int tf_dwconv7_wgrad_f32(const float* dy, const float* x, float* dw, float* dbias, int B, int H, int W, int C, void* stream) {
     TF_REQUIRE(dy && x && dw && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && aligned16(x) && aligned16(dy), "tf_dwconv7_wgrad_f32: needs C %% 4 == 0, 16-byte aligned");
+    TF_REQUIRE(!deterministic(), "tf_dwconv7_wgrad_f32: the row blocks are combined with fp32 atomics and there is no fixed-order form - refused under tf_set_deterministic(1)");
+    float_atomic_count(1);
     const long npix = (long)B * H * W;
     long bx = (npix + 16 * 64 - 1) / (16 * 64);      // >= 64 pixels per pixel lane
     if (bx > 128) bx = 128;

@@ -19,7 +19,15 @@ int smallm_dgrad(const float* dy, long lddy, const float* w, long ldw, const flo
                  int accumulate, void* stream);
 int smallm_wgrad(const float* dy, long lddy, const float* x, long ldx, float* dw, long lddw, int M, int N, int K, int accumulate, void* stream);
 bool skinny_wgrad_ok(int no, int C, int rows, long lddy, long ldx, const float* x, int accumulate);
-int skinny_wgrad(const float* dy, long lddy, const float* x, long ldx, float* dw, long lddw, int rows, int no, int C, void* stream);
+int skinny_wgrad(const float* dy, long lddy, const float* x, long ldx, float* dw, long lddw, int rows, int no, int C, float* ws, long ws_floats, void* stream);
+long skinny_wgrad_ws_floats(int rows, int no, int C);
+}
+
+// does this call take the skinny weight-gradient kernels (smallm.cpp) instead of the engine?
+static bool skinny_route(const tf_gemm_desc* d) {
+    static const bool skinny = [] { const char* e = getenv("TF_SKINNY_WGRAD"); return e ? e[0] != '0' : true; }();
+    return skinny && d->batch == 1 && d->alpha == 1.0f && d->m > 0 && d->n > 0 && d->k > 16 && !d->mask && !d->colstat && !d->drop_seed && d->a_trans && d->b_trans &&
+           !d->bias && !d->res && !d->relu && (gemm_precision() == 0 || gemm_precision() == 2) && skinny_wgrad_ok(d->m, d->n, d->k, d->lda, d->ldb, d->b, d->accumulate);
 }
 
 static PlainOp make_plain(const float* p, long ld, int rows, int cols, long so, long si, int inner, int batch) {
@@ -36,13 +44,17 @@ static PlainOp make_plain(const float* p, long ld, int rows, int cols, long so, 
 // maximum while the autotuner is on or a test pins a two-pass plan (the candidates need the scratch to be tried at all).
 extern "C" long tf_gemm_splitk_ws_floats(const tf_gemm_desc* d) {
     if (!d || d->batch != 1 || d->m <= 0 || d->n <= 0 || d->k <= 0) return 0;
+    const bool det_acc = deterministic() && d->accumulate && !d->bias && !d->res && !d->relu;      // tf_set_deterministic: the fixed-order forms of the accumulating calls
+    if (det_acc && skinny_route(d)) return skinny_wgrad_ws_floats(d->k, d->m, d->n);
     const long slice = (long)d->m * twopass_ldws(d->n);
     GemmPlan p;
     const long sk_floats = (long)kStreamKMaxBlocks / 4 * 128 * 128;       // stream-K: <= 512 resident workgroups x one 128 x 128 partial tile (larger launches use smaller tiles)
-    if (forced_plan(&p)) return p.splitk == kStreamK ? sk_floats : p.splitk >= kTwoPass ? 4 * slice : 0;
     const char* site = !d->a_trans ? (d->b_trans ? "tf_gemm_f32[nn]" : "tf_gemm_f32[nt]") : (d->b_trans ? "tf_gemm_f32[tn]" : "tf_gemm_f32[tt]");
     int M = d->m, N = d->n;
-    if (d->a_trans && d->b_trans && d->m <= 32 && d->n >= 2 * d->m && !d->bias && !d->res && !d->relu) return 0;       // swapped (column-strided) output: no two-pass
+    if (det_acc && d->a_trans && d->b_trans) { const long need = slab_ws_floats(site, M, N, d->k); if (need > 0) return need; }      // ordered slab k-split (the swapped orientation is not taken in this mode)
+    if (forced_plan(&p)) return p.splitk == kStreamK ? sk_floats : p.splitk >= kTwoPass ? 4 * slice : 0;
+    if (det_acc) {}
+    else if (d->a_trans && d->b_trans && d->m <= 32 && d->n >= 2 * d->m && !d->bias && !d->res && !d->relu) return 0;       // swapped (column-strided) output: no two-pass
     const bool sk_ok = d->accumulate && !d->bias && !d->res && !d->relu;
     const int acc = (d->accumulate ? (sk_ok ? 2 : 1) : 0) + 4 * (gemm_precision() == 3 ? 1 : gemm_precision());
     if (plan_lookup(site, M, N, d->k, 1, acc, &p)) return p.splitk == kStreamK ? sk_floats : p.splitk >= kTwoPass ? (long)(p.splitk - kTwoPass) * slice : 0;
@@ -63,10 +75,8 @@ extern "C" int tf_gemm_f32(const tf_gemm_desc* d, void* stream) {
         if (d->a_trans && d->b_trans && d->k <= 16 && !d->bias && !d->res && !d->relu)
             return smallm_wgrad(d->a, d->lda, d->b, d->ldb, d->c, d->ldc, d->k, d->m, d->n, d->accumulate, stream);
         // few output features over many rows (head convolutions 64 -> 1 / 2 / 3 / 12): streaming reduction instead of a 160-way split 128 x 32 tile
-        static const bool skinny = [] { const char* e = getenv("TF_SKINNY_WGRAD"); return e ? e[0] != '0' : true; }();
-        if (skinny && d->a_trans && d->b_trans && !d->bias && !d->res && !d->relu && (gemm_precision() == 0 || gemm_precision() == 2) &&
-            skinny_wgrad_ok(d->m, d->n, d->k, d->lda, d->ldb, d->b, d->accumulate))
-            return skinny_wgrad(d->a, d->lda, d->b, d->ldb, d->c, d->ldc, d->k, d->m, d->n, stream);
+        if (skinny_route(d))
+            return skinny_wgrad(d->a, d->lda, d->b, d->ldb, d->c, d->ldc, d->k, d->m, d->n, d->splitk_ws, d->splitk_ws ? d->splitk_ws_floats : 0, stream);
     }
     GemmEpi ep;
     ep.C = d->c; ep.ldc = d->ldc; ep.ldcj = 1; ep.sc_outer = d->sc_outer; ep.sc_inner = d->sc_inner; ep.inner = inner;
@@ -99,7 +109,8 @@ extern "C" int tf_gemm_f32(const tf_gemm_desc* d, void* stream) {
     if (d->a_trans && d->b_trans) {
         // weight gradient with few output rows (m = out features <= 32 << n): compute C^T so the short side becomes the
         // 32-wide column tile instead of a 128-row tile (4x less MFMA padding); stores go through the column stride.
-        if (d->m <= 32 && d->n >= 2 * d->m && !d->bias && !d->res && !d->relu) {
+        // (not in the deterministic mode: the ordered slab k-split needs a row-major output, so that mode keeps the unswapped orientation)
+        if (d->m <= 32 && d->n >= 2 * d->m && !d->bias && !d->res && !d->relu && !(deterministic() && d->accumulate)) {
             ep.ldc = 1; ep.ldcj = d->ldc;
             return gemm_plain_tn(B, A, ep, d->n, d->m, d->k, d->batch, sk, stream, "tf_gemm_f32[tn,swapped]");
         }

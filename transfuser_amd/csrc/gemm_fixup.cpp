@@ -2,6 +2,7 @@
 // few tiles for the 256 CUs stored raw partial tiles ws[s][M][ldws]; here they are summed IN SLICE ORDER (bitwise reproducible, unlike the
 // atomic split-K of the weight gradients) and the GEMM epilogue proper is applied: alpha, bias, residual, ReLU, mask, store / +=.
 // HBM-bound: (S + res + mask) reads + one write of the M x N output, float4 where the output allows it.
+// The deterministic mode (tf_set_deterministic) sends the k-slices of every accumulating weight gradient through here as well (any S).
 #include "tf_gemm_engine.h"
 
 namespace tf {
@@ -18,7 +19,26 @@ __global__ void __launch_bounds__(256) splitk_fixup_kernel(const float* __restri
 #pragma unroll
     for (int e = 0; e < V; ++e) v[e] = 0.f;
     const float* p = ws + (long)i * ldws + j;
-    for (int s = 0; s < nsplit; ++s) {
+    int s = 0;
+    // the ordered slab k-split of the deterministic mode hands over as many slices as the atomic plan it replaces had (up to hundreds for the
+    // high-resolution layers): 16, then 4 loads in flight per trip instead of a chain of single round trips; the adds keep the slice order
+    auto trip = [&](auto n_c) {
+        constexpr int U = decltype(n_c)::value;
+        for (; s + U <= nsplit; s += U) {
+            float t[U][V];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (V4) { const float4 q = *reinterpret_cast<const float4*>(p + (long)(s + u) * sk_stride); t[u][0] = q.x; t[u][1 % V] = q.y; t[u][2 % V] = q.z; t[u][3 % V] = q.w; }
+                else t[u][0] = p[(long)(s + u) * sk_stride];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int e = 0; e < V; ++e) v[e] += t[u][e];
+        }
+    };
+    if (nsplit > 4) { trip(std::integral_constant<int, 16>()); trip(std::integral_constant<int, 4>()); }
+    for (; s < nsplit; ++s) {
         if (V4) {
             const float4 t = *reinterpret_cast<const float4*>(p + (long)s * sk_stride);
             v[0] += t.x; v[1 % V] += t.y; v[2 % V] += t.z; v[3 % V] += t.w;

@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(256) layernorm_bwd_dw_kernel(const float* __re
 #pragma unroll
             for (int u = 0; u < 4; ++u)
                 if (r + 4 * u < r1) {
-                    ag += d[u] * ((xv[u] - m[u]) * rs[u]);
+                    ag += ln_dgamma_term(d[u], xv[u], m[u], rs[u]);
                     ab += d[u];
                 }
         }
@@ -302,6 +302,7 @@ extern "C" int tf_layernorm_fwd16_f32(const float* x, const float* gamma, const 
 
 static int layernorm_bwd_impl(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, float* dx,
                               int dx_accumulate, float* dgamma, float* dbeta, int rows, int C, LnDrop dr, void* stream, const char* what) {
+    TF_REQUIRE(!(deterministic() && dgamma && dbeta), "%s: dgamma / dbeta end in fp32 atomics here - under tf_set_deterministic(1) pass NULL and call tf_layernorm_bwd_dw_f32", what);
     if (rows == 0) return 0;
     switch (ln_nv(C, dy, x, gamma) && aligned16(dx) && (!dr.out || aligned16(dr.out)) ? ln_nv(C, dy, x, gamma) : 0) {
 #define TF_LNB(NV_) case NV_: TF_LAUNCH(layernorm_bwd_dx_v4_kernel<NV_>, dim3(cdiv(rows, 4)), dim3(256), stream, dy, x, gamma, mean, rstd, dx, rows, C, dx_accumulate, dr); break
@@ -311,6 +312,7 @@ static int layernorm_bwd_impl(const float* dy, const float* x, const float* gamm
     }
     if (dgamma && dbeta) {
         const int rpb = 64;
+        float_atomic_count(1);
         TF_LAUNCH(layernorm_bwd_dw_kernel, dim3(cdiv(C, 64), cdiv(rows, rpb)), dim3(256), stream, dy, x, mean, rstd, dgamma, dbeta, rows,
                   C, rpb);
     }

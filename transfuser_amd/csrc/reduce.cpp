@@ -187,6 +187,17 @@ template <class G> struct BnBwdF {  // (g, g * xhat)
     }
 };
 
+struct LnDwF {  // (dy * xhat, dy): the LayerNorm weight / bias gradient terms of one row; mean / rstd are per ROW
+    const float* dy; const float* x; const float* mean; const float* rstd; int C;
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+        const long e = row * C + c;
+        const vecf<V> g = ldv<V>(dy + e), a = ldv<V>(x + e);
+        const float m = mean[row], rs = rstd[row];
+#pragma unroll
+        for (int i = 0; i < V; ++i) { o[0].v[i] = ln_dgamma_term(g.v[i], a.v[i], m, rs); o[1].v[i] = g.v[i]; }
+    }
+};
+
 // (A "last block finishes" form of this kernel - partials at agent scope, a ticket per column tile, the last block finalizes - removed ~270 finalize
 // launches per step and was measured SLOWER: 55.6 vs 51.6 ms/step, 66.7 with __threadfence(); DESIGN section 3.  It is gone since round 5.)
 template <int V, int NACC, class F>
@@ -322,6 +333,18 @@ __global__ void __launch_bounds__(256) colsum_finalize_kernel(const float* __res
     const int seg = live ? i / C : 0, c = live ? i - seg * C : 0;
     float s = chunk_sum(ws + (long)seg * nch * C + c, C, nch, lane, live) * scale;
     if (live && lane == 0) { if (accumulate) out[i] += s; else out[i] = s; }
+}
+
+// dgamma[c] += sum_chunks ws[chunk][0][c], dbeta[c] += sum_chunks ws[chunk][1][c] (the LnDwF partials; fixed order: lanes own chunks, then the shuffle tree)
+__global__ void __launch_bounds__(256) ln_dw_finalize_kernel(const float* __restrict__ ws, float* __restrict__ dgamma, float* __restrict__ dbeta, int C, int nch) {
+    const int c0 = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const bool live = c0 < C;
+    const int c = live ? c0 : 0;
+    float s1, s2;
+    chunk_sum2(ws + c, ws + C + c, 2L * C, nch, lane, live, s1, s2);
+    if (!live || lane != 0) return;
+    dgamma[c] += s1;
+    dbeta[c] += s2;
 }
 
 // BN training statistics (torch BatchNorm2d train mode: biased var for normalisation, unbiased for
@@ -724,6 +747,17 @@ inline const float* bn_bwd_sums(const G& grad, bool allow_vec, const float* x, i
 }
 }  // namespace
 
+// LayerNorm dgamma / dbeta in fixed summation order (include/transfuser_hip.h): chunk partials + ln_dw_finalize_kernel, no atomics
+extern "C" int tf_layernorm_bwd_dw_f32(const float* dy, const float* x, const float* mean, const float* rstd, float* dgamma, float* dbeta, int rows, int C, float* ws,
+                                       void* stream) {
+    TF_REQUIRE(dy && x && mean && rstd && dgamma && dbeta && ws && rows >= 0 && C > 0, "tf_layernorm_bwd_dw_f32: bad arguments");
+    if (rows == 0) return 0;
+    const RedPlan p = plan_reduce(rows, C, 1, 2, aligned16(dy) && aligned16(x));
+    launch_reduce<2>(p, LnDwF{dy, x, mean, rstd, C}, rows, C, 1, ws, stream);
+    TF_LAUNCH(ln_dw_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, dgamma, dbeta, C, p.nchunks);
+    return launch_status("tf_layernorm_bwd_dw_f32");
+}
+
 extern "C" long tf_workspace_bytes(void) { return (kWsFloats + kTickets) * 4; }
 extern "C" int tf_bn_zacc_floats(int C) { return kBnSlots * 2 * C; }
 
@@ -734,11 +768,13 @@ extern "C" int tf_bn_fwd_f32(const float* x, int rows, int C, const float* gamma
                              int training, float* zacc, void* stream) {
     TF_REQUIRE(x && gamma && beta && y && ws && rows > 0 && C > 0, "tf_bn_fwd_f32: bad arguments");
     float* coef = ws + kWsFloats / 2;
+    if (deterministic()) zacc = nullptr;      // tf_set_deterministic: the opt-in atomically accumulated statistics (TF_ATOMIC_BN) are ignored
     if (training && zacc) {   // 2 launches: atomically accumulated statistics, then a column-owned normalise pass (no finalize kernel)
         TF_REQUIRE(save_mean && save_invstd, "tf_bn_fwd_f32: training needs save_mean/save_invstd");
         const bool v4ok = aligned16(x) && aligned16(y) && (!res || aligned16(res));
         RedPlan p = plan_reduce(rows, C, 1, 2, v4ok);
         const BnStatF f{x, x, C};
+        float_atomic_count(1);
         launch_reduce<2>(p, f, rows, C, 1, zacc, stream, 2, 1.f);
         dim3 grid(p.coltiles, p.nchunks);
         if (p.V == 4) TF_LAUNCH(bn_apply_cols_kernel<4>, grid, dim3(256), stream, x, (const float*)zacc, gamma, beta, running_mean, running_var, save_mean,
@@ -781,9 +817,11 @@ extern "C" int tf_bn_bwd_f32(const float* dz, const float* z, const float* x, in
                              const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, float* ws, float* zacc, void* stream) {
     TF_REQUIRE(dz && x && gamma && save_mean && save_invstd && dx && ws && rows > 0 && C > 0, "tf_bn_bwd_f32: bad arguments");
     const GradZ grad{dz, z};
+    if (deterministic()) zacc = nullptr;
     if (zacc) {
         const bool v4ok = aligned16(dz) && aligned16(x) && aligned16(dx) && (!z || aligned16(z)) && (!dres || aligned16(dres));
         RedPlan p = plan_reduce(rows, C, 1, 2, v4ok);
+        float_atomic_count(1);
         launch_reduce<2>(p, BnBwdF<GradZ>{grad, x, save_mean, save_invstd, C}, rows, C, 1, zacc, stream, 2, 1.f);
         dim3 grid(p.coltiles, p.nchunks);
         if (p.V == 4) TF_LAUNCH(bn_bwd_apply_cols_kernel<4>, grid, dim3(256), stream, dz, z, x, (const float*)zacc, gamma, save_mean, save_invstd, dgamma,
@@ -806,7 +844,8 @@ extern "C" int tf_colsum_f32(const float* x, const float* mask, int nseg, int ro
     RedPlan p = plan_reduce(rows_per_seg, C, nseg, 1, aligned16(x) && (!mask || aligned16(mask)));
     const MaskSumF f{x, mask, C};
     static const bool atomic_colsum = [] { const char* e = getenv("TF_ATOMIC_COLSUM"); return e ? e[0] != '0' : false; }();   // measured slower on the MI355X (165.4 vs 167.1 samples/s): opt-in
-    if (accumulate && atomic_colsum) {   // += : the blocks add straight into the destination with fp32 atomics - one launch, no partials, no finalize
+    if (accumulate && atomic_colsum && !deterministic()) {   // += : the blocks add straight into the destination with fp32 atomics - one launch, no partials, no finalize
+        float_atomic_count(1);
         launch_reduce<1>(p, f, rows_per_seg, C, nseg, out, stream, 1, scale);
         return launch_status("tf_colsum_f32");
     }

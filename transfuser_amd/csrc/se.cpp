@@ -164,11 +164,12 @@ __global__ void __launch_bounds__(256) se_zero_kernel(float* __restrict__ p, int
 }
 
 // fc2 pass, one block per SE_ROWS rows n of W2:  dW2[n][:] += dgate[:,n]^T g1,  db2[n] += sum_b dgate[b][n],
-// and this slice's contribution to dg1[b][j] = sum_n dgate[b][n] W2[n][j] (atomics into the zeroed scratch).
+// and this slice's contribution to dg1[b][j] = sum_n dgate[b][n] W2[n][j] (atomics into the zeroed scratch; slabs != 0, the deterministic mode:
+// a plain store into this block's own (B, Cr) slab dg1[block][b][j], which the fc1 pass adds up in block order).
 constexpr int SE_ROWS = 8;
 __global__ void __launch_bounds__(256) se_excite_bwd2_kernel(const float* __restrict__ dgate, const float* __restrict__ g1, const float* __restrict__ W2,
                                                              int B, int C, int Cr, float* __restrict__ dW2, float* __restrict__ db2,
-                                                             float* __restrict__ dg1, float* __restrict__ ds_zero, int nch = 0,
+                                                             float* __restrict__ dg1, float* __restrict__ ds_zero, int slabs, int nch = 0,
                                                              const float* __restrict__ gate = nullptr) {
     __shared__ float dgs[SE_MAXB][SE_ROWS];
     // ds (B x C) is ACCUMULATED by the j-sliced fc1 pass that follows: cleared here, one slice per block
@@ -224,25 +225,38 @@ __global__ void __launch_bounds__(256) se_excite_bwd2_kernel(const float* __rest
             for (int b = 0; b < SE_MAXB; ++b)
                 if (b < B) acc[b] += dgs[b][r] * w;
         }
+        float* slab = dg1 + (long)blockIdx.x * B * Cr;
 #pragma unroll
         for (int b = 0; b < SE_MAXB; ++b)
-            if (b < B) atomicAdd(dg1 + b * Cr + j, acc[b]);
+            if (b < B) {
+                if (slabs) slab[b * Cr + j] = acc[b];
+                else atomicAdd(dg1 + b * Cr + j, acc[b]);
+            }
     }
 }
 
 // fc1 pass, one block per (32 columns k of W1, slice of the Cr rows j):  dg = dg1 * (g1 > 0);  dW1[j][k] += sum_b dg[b][j] s[b][k];
 // db1[j] += sum_b dg[b][j] (column block 0);  ds[b][k] += sum_{j in slice} dg[b][j] W1[j][k] (fp32 atomics into the buffer the fc2 pass
 // cleared: SE_JS j-slices give C / 32 x SE_JS blocks instead of 18-47 - the kernel was a 23 us latency chain on a 10 % filled GPU).
+// nslab > 0 (deterministic mode): dg1 arrives as nslab (B, Cr) slabs of the fc2 pass, summed here in slab order while dg is staged, and the grid has ONE
+// j-slice per column block, which therefore owns its ds columns and stores them.
 constexpr int SE_JS = 6;
 __global__ void __launch_bounds__(256) se_excite_bwd1_kernel(const float* __restrict__ dg1, const float* __restrict__ g1, const float* __restrict__ s,
                                                              const float* __restrict__ W1, int B, int C, int Cr, float* __restrict__ dW1,
-                                                             float* __restrict__ db1, float* __restrict__ ds) {
+                                                             float* __restrict__ db1, float* __restrict__ ds, int nslab) {
     __shared__ float dgm[SE_MAXB * SE_MAXR / 2];
     __shared__ float ssl[SE_MAXB][32];
     __shared__ float red[8][SE_MAXB][32];
     const int tid = threadIdx.x, kx = tid & 31, jg = tid >> 5;
     const int k = blockIdx.x * 32 + kx;
-    const int jper = (Cr + SE_JS - 1) / SE_JS, j0 = blockIdx.y * jper, j1 = (j0 + jper < Cr) ? j0 + jper : Cr;
+    const int jper = nslab ? Cr : (Cr + SE_JS - 1) / SE_JS, j0 = blockIdx.y * jper, j1 = (j0 + jper < Cr) ? j0 + jper : Cr;
+    if (nslab) {
+        for (int i = tid; i < B * Cr; i += 256) {
+            float v = 0.f;
+            for (int sl = 0; sl < nslab; ++sl) v += dg1[(long)sl * B * Cr + i];
+            dgm[i] = g1[i] > 0.f ? v : 0.f;
+        }
+    } else
     for (int i = tid; i < B * Cr; i += 256) dgm[i] = g1[i] > 0.f ? dg1[i] : 0.f;
     for (int i = tid; i < B * 32; i += 256) {
         const int b = i >> 5, c = blockIdx.x * 32 + (i & 31);
@@ -285,7 +299,8 @@ __global__ void __launch_bounds__(256) se_excite_bwd1_kernel(const float* __rest
             float v = 0.f;
 #pragma unroll
             for (int g = 0; g < 8; ++g) v += red[g][b][kx];
-            atomicAdd(ds + (long)b * C + k, v);
+            if (nslab) ds[(long)b * C + k] = v;
+            else atomicAdd(ds + (long)b * C + k, v);
         }
     if (blockIdx.x == 0 && db1)
         for (int j = j0 + tid; j < j1; j += 256) {
@@ -311,9 +326,11 @@ extern "C" int tf_se_excite_bwd_f32(const float* dgate, const float* s, const fl
                                     float* dW1, float* db1, float* dW2, float* db2, float* ds, float* scratch, int scratch_is_zero, void* stream) {
     TF_REQUIRE(dgate && s && g1 && W1 && W2 && dW1 && dW2 && ds && scratch && B > 0 && B <= SE_MAXB && C > 0 && Cr > 0 &&
                    (long)B * Cr <= SE_MAXB * SE_MAXR / 2, "tf_se_excite_bwd_f32: bad arguments (B <= 16, B*Cr <= 8192)");
-    if (!scratch_is_zero) TF_LAUNCH(se_zero_kernel, dim3(cdiv((long)B * Cr, 256)), dim3(256), stream, scratch, B * Cr);
-    TF_LAUNCH(se_excite_bwd2_kernel, dim3(cdiv(C, SE_ROWS)), dim3(256), stream, dgate, g1, W2, B, C, Cr, dW2, db2, scratch, ds);
-    TF_LAUNCH(se_excite_bwd1_kernel, dim3(cdiv(C, 32), SE_JS), dim3(256), stream, (const float*)scratch, g1, s, W1, B, C, Cr, dW1, db1, ds);
+    const int det = deterministic() ? 1 : 0, nslab = det ? cdiv(C, SE_ROWS) : 0;      // deterministic mode: scratch holds tf_se_excite_bwd_ws_floats() floats
+    if (!det) float_atomic_count(1);
+    if (!scratch_is_zero && !det) TF_LAUNCH(se_zero_kernel, dim3(cdiv((long)B * Cr, 256)), dim3(256), stream, scratch, B * Cr);
+    TF_LAUNCH(se_excite_bwd2_kernel, dim3(cdiv(C, SE_ROWS)), dim3(256), stream, dgate, g1, W2, B, C, Cr, dW2, db2, scratch, ds, det);
+    TF_LAUNCH(se_excite_bwd1_kernel, dim3(cdiv(C, 32), det ? 1 : SE_JS), dim3(256), stream, (const float*)scratch, g1, s, W1, B, C, Cr, dW1, db1, ds, nslab);
     return launch_status("tf_se_excite_bwd_f32");
 }
 
@@ -334,8 +351,16 @@ extern "C" int tf_se_excite_bwd_parts_f32(const float* parts, int nchunks, const
                                           void* stream) {
     TF_REQUIRE(parts && nchunks > 0 && gate && s && g1 && W1 && W2 && dW1 && dW2 && ds && scratch && B > 0 && B <= SE_MAXB && C > 0 && Cr > 0 &&
                    (long)B * Cr <= SE_MAXB * SE_MAXR / 2, "tf_se_excite_bwd_parts_f32: bad arguments (B <= 16, B*Cr <= 8192)");
-    if (!scratch_is_zero) TF_LAUNCH(se_zero_kernel, dim3(cdiv((long)B * Cr, 256)), dim3(256), stream, scratch, B * Cr);
-    TF_LAUNCH(se_excite_bwd2_kernel, dim3(cdiv(C, SE_ROWS)), dim3(256), stream, parts, g1, W2, B, C, Cr, dW2, db2, scratch, ds, nchunks, gate);
-    TF_LAUNCH(se_excite_bwd1_kernel, dim3(cdiv(C, 32), SE_JS), dim3(256), stream, (const float*)scratch, g1, s, W1, B, C, Cr, dW1, db1, ds);
+    const int det = deterministic() ? 1 : 0, nslab = det ? cdiv(C, SE_ROWS) : 0;
+    if (!det) float_atomic_count(1);
+    if (!scratch_is_zero && !det) TF_LAUNCH(se_zero_kernel, dim3(cdiv((long)B * Cr, 256)), dim3(256), stream, scratch, B * Cr);
+    TF_LAUNCH(se_excite_bwd2_kernel, dim3(cdiv(C, SE_ROWS)), dim3(256), stream, parts, g1, W2, B, C, Cr, dW2, db2, scratch, ds, det, nchunks, gate);
+    TF_LAUNCH(se_excite_bwd1_kernel, dim3(cdiv(C, 32), det ? 1 : SE_JS), dim3(256), stream, (const float*)scratch, g1, s, W1, B, C, Cr, dW1, db1, ds, nslab);
     return launch_status("tf_se_excite_bwd_parts_f32");
+}
+
+// floats of `scratch` the two backward entries above use: one (B, Cr) accumulator, or one slab per fc2 block under tf_set_deterministic(1)
+extern "C" long tf_se_excite_bwd_ws_floats(int B, int C, int Cr) {
+    if (B <= 0 || C <= 0 || Cr <= 0) return 0;
+    return (long)(deterministic() ? cdiv(C, SE_ROWS) : 1) * B * Cr;
 }

@@ -44,6 +44,9 @@ __global__ void __launch_bounds__(256) smallm_fwd_kernel(const float* __restrict
 // dx[m][k] (+)= sum_n dy[m][n] * w[n][k] (+ res): block = 32 k-columns x 8 n-slices of ONE n-chunk (grid.y chunks);
 // partial sums are combined through LDS and, across chunks, with fp32 atomics into a destination that the first chunk
 // initialises (res / old value / 0) - so the grid has K/32 x N/256 blocks instead of K/32.
+// ORDERED (deterministic mode, tf_set_deterministic): the launch has ONE chunk (nchunk = N), so the block owns its 32 columns and adds its sum to the
+// initialised destination with a plain read-modify-write: the same sums in a fixed order, K/32 blocks.
+template <bool ORDERED>
 __global__ void __launch_bounds__(256) smallm_dgrad_kernel(const float* __restrict__ dy, long lddy, const float* __restrict__ w, long ldw,
                                                            float* __restrict__ dx, long lddx, int M, int N, int K, int nchunk) {
     __shared__ float red[8][SM_MAXM][32];
@@ -69,7 +72,8 @@ __global__ void __launch_bounds__(256) smallm_dgrad_kernel(const float* __restri
             float v = 0.f;
 #pragma unroll
             for (int s = 0; s < 8; ++s) v += red[s][m][kx];
-            atomicAdd(dx + m * lddx + k, v);
+            if (ORDERED) dx[m * lddx + k] += v;
+            else atomicAdd(dx + m * lddx + k, v);
         }
     }
 }
@@ -99,9 +103,10 @@ __global__ void __launch_bounds__(256) smallm_wgrad_kernel(const float* __restri
 // six heads per step; here it is a streaming reduction: a block walks a row chunk, thread (tx, ty) holds dW[0..NO)[4 tx .. 4 tx + 3] for the rows
 // ty, ty + RL, ...; the row lanes are combined through LDS and the block adds its partial to dW with fp32 atomics (as the engine's split-K
 // weight gradients do).  dw[o][c] += sum_r dy[r][o] * x[r][c];  C % 4 == 0, C <= 256, NO <= 16.
+// slab != NULL (deterministic mode): the block STORES its partial to slab[block][o][c] instead; skinny_wgrad_reduce_kernel adds the blocks to dW in block order.
 template <int NO>
 __global__ void __launch_bounds__(256) skinny_wgrad_kernel(const float* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx, float* __restrict__ dw,
-                                                           long lddw, int rows, int no, int C, int rows_per_block) {
+                                                           long lddw, int rows, int no, int C, int rows_per_block, float* __restrict__ slab) {
     __shared__ float4 red[256];
     const int cv = C >> 2, RL = 256 / cv;
     const int tx = threadIdx.x % cv, ty = threadIdx.x / cv;
@@ -149,24 +154,47 @@ __global__ void __launch_bounds__(256) skinny_wgrad_kernel(const float* __restri
         if (ty == 0 && o < no) {
             float4 t = red[tx];
             for (int j = 1; j < RL; ++j) { const float4 v = red[j * cv + tx]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-            float* d = dw + (long)o * lddw + 4 * tx;
-            atomicAdd(d, t.x); atomicAdd(d + 1, t.y); atomicAdd(d + 2, t.z); atomicAdd(d + 3, t.w);
+            if (slab) *reinterpret_cast<float4*>(slab + ((long)blockIdx.x * no + o) * C + 4 * tx) = t;
+            else {
+                float* d = dw + (long)o * lddw + 4 * tx;
+                atomicAdd(d, t.x); atomicAdd(d + 1, t.y); atomicAdd(d + 2, t.z); atomicAdd(d + 3, t.w);
+            }
         }
     }
 }
+// dw[o][c] += sum_blocks slab[block][o][c], blocks in ascending order (one thread per element, loads of consecutive threads coalesce)
+__global__ void __launch_bounds__(256) skinny_wgrad_reduce_kernel(const float* __restrict__ slab, int nblocks, float* __restrict__ dw, long lddw, int no, int C) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= no * C) return;
+    float t = 0.f;
+    for (int b = 0; b < nblocks; ++b) t += slab[(long)b * no * C + i];
+    const int o = i / C, c = i - o * C;
+    dw[(long)o * lddw + c] += t;
+}
+constexpr int kSkinnyMaxBlocks = 96;
 bool skinny_wgrad_ok(int no, int C, int rows, long lddy, long ldx, const float* x, int accumulate) {
     return accumulate && no >= 1 && no <= 16 && C % 4 == 0 && C >= 16 && C <= 256 && rows >= 4096 && ldx % 4 == 0 && aligned16(x) && lddy >= no;
 }
-int skinny_wgrad(const float* dy, long lddy, const float* x, long ldx, float* dw, long lddw, int rows, int no, int C, void* stream) {
+long skinny_wgrad_ws_floats(int, int no, int C) { return (long)kSkinnyMaxBlocks * no * C; }
+int skinny_wgrad(const float* dy, long lddy, const float* x, long ldx, float* dw, long lddw, int rows, int no, int C, float* ws, long ws_floats, void* stream) {
     // every block ends with NO x C atomics on the SAME addresses, which the memory side serialises (320 blocks: 36 us, mostly that queue):
     // few, fat blocks
     int blocks = cdiv(rows, 512);
-    if (blocks > 96) blocks = 96;
+    if (blocks > kSkinnyMaxBlocks) blocks = kSkinnyMaxBlocks;
+    float* slab = nullptr;
+    if (deterministic()) {      // block partials in the caller's scratch (tf_gemm_desc.splitk_ws), as many blocks as it holds; none: one block walks every row
+        const long fit = ws ? ws_floats / ((long)no * C) : 0;
+        TF_REQUIRE(!ws || aligned16(ws), "tf_gemm_f32[skinny wgrad]: splitk_ws must be 16-byte aligned");
+        if (fit < blocks) blocks = fit >= 1 ? (int)fit : 1;
+        if (fit >= 1) slab = ws;
+    }
     const int rpb = cdiv(rows, blocks);
     blocks = cdiv(rows, rpb);
-#define TF_SK(NO_) TF_LAUNCH(skinny_wgrad_kernel<NO_>, dim3(blocks), dim3(256), stream, dy, lddy, x, ldx, dw, lddw, rows, no, C, rpb)
+    if (!slab && blocks > 1) float_atomic_count(1);
+#define TF_SK(NO_) TF_LAUNCH(skinny_wgrad_kernel<NO_>, dim3(blocks), dim3(256), stream, dy, lddy, x, ldx, dw, lddw, rows, no, C, rpb, slab)
     if (no <= 1) TF_SK(1); else if (no <= 2) TF_SK(2); else if (no <= 4) TF_SK(4); else if (no <= 8) TF_SK(8); else TF_SK(16);
 #undef TF_SK
+    if (slab) TF_LAUNCH(skinny_wgrad_reduce_kernel, dim3(cdiv((long)no * C, 256)), dim3(256), stream, (const float*)slab, blocks, dw, lddw, no, C);
     return launch_status("tf_gemm_f32[skinny wgrad]");
 }
 
@@ -179,7 +207,11 @@ int smallm_dgrad(const float* dy, long lddy, const float* w, long ldw, const flo
                  int accumulate, void* stream) {
     if (!accumulate) TF_LAUNCH(smallm_init_kernel, dim3(cdiv((long)M * K, 256)), dim3(256), stream, dx, lddx, res, ldres, M, K);
     const int nchunk = 256;
-    TF_LAUNCH(smallm_dgrad_kernel, dim3(cdiv(K, 32), cdiv(N, nchunk)), dim3(256), stream, dy, lddy, w, ldw, dx, lddx, M, N, K, nchunk);
+    if (deterministic()) TF_LAUNCH(smallm_dgrad_kernel<true>, dim3(cdiv(K, 32), 1), dim3(256), stream, dy, lddy, w, ldw, dx, lddx, M, N, K, N);
+    else {
+        float_atomic_count(1);
+        TF_LAUNCH(smallm_dgrad_kernel<false>, dim3(cdiv(K, 32), cdiv(N, nchunk)), dim3(256), stream, dy, lddy, w, ldw, dx, lddx, M, N, K, nchunk);
+    }
     return launch_status("tf_gemm_f32[small-m dgrad]");
 }
 int smallm_wgrad(const float* dy, long lddy, const float* x, long ldx, float* dw, long lddw, int M, int N, int K, int accumulate, void* stream) {

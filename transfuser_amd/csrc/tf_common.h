@@ -8,6 +8,9 @@ namespace tf {
 
 void set_error(const char* fmt, ...);  // api.cpp
 bool ablated(const char* kernel);      // api.cpp: TF_ABLATE=substr[,substr...] turns the matching kernels' launches into no-ops (timing diagnosis only)
+bool deterministic();                  // api.cpp: tf_set_deterministic - every reduction that would end in fp32 atomics takes its fixed-order form (or refuses); read on the host at launch time
+long float_atomic_count(int add);      // api.cpp: launches of kernel forms that combine partial results with float atomics (tf_float_atomic_launches)
+long slab_splitk_count(int add);       // api.cpp: launches of the ordered slab k-split of the MFMA engine (tf_slab_splitk_launches)
 
 #ifdef TF_EMU
 #define TF_LAUNCH_AS(name, kern, grid, block, stream, ...)               \

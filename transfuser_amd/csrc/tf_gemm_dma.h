@@ -489,6 +489,7 @@ inline void launch_dma_cfg(const PlainOp& la, const PlainOp& lb, const GemmEpi& 
         if (g > tiles_m) g = tiles_m;
         epg.group_m = (g >= 2 && tiles_n >= 4) ? g : 1;
     }
+    if (epg.mode == 2) float_atomic_count(1);
     if (twopass || nsplit > 1) epg.stat = nullptr;          // (launch_gemm never sends a statistics request down a k-split plan)
     if (epg.stat_nparts) *epg.stat_nparts = epg.stat ? cdiv(M, 32 * TM) : 0;
     if (epg.prec == 2 && !ep.packed16)

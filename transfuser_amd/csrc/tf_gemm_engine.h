@@ -243,7 +243,7 @@ struct GemmEpi {
     float alpha; int relu; int mode; // mode 0: store, 1: +=, 2: atomicAdd
     int group_m = 1;                 // tile rasterisation: rows of tiles walked together (set by launch_cfg)
     const float* mask = nullptr; long ldmask = 0;   // optional ReLU mask of a backward GEMM: element (i, j) is zeroed unless mask(i, j) > 0
-    long sk_stride = 0;              // two-pass split-K: k-slice blockIdx.y stores its partial tile at C + blockIdx.y * sk_stride (LDS-DMA kernels)
+    long sk_stride = 0;              // two-pass / ordered slab split-K: k-slice blockIdx.y stores its partial tile at C + blockIdx.y * sk_stride
     float* sk_ws = nullptr; long sk_ws_floats = 0;   // caller-owned scratch that makes the two-pass split-K / stream-K eligible (tf_gemm_desc); read on the device by the stream-K kernels
     int* sk_flags = nullptr;         // stream-K: kStreamKMaxBlocks hand-over flags, zero between launches (caller-owned, persistent; tf_gemm_desc.sk_flags)
     // BatchNorm statistics of the OUTPUT, fused into the epilogue (train-mode BN behind a bias-free conv, timm BatchNormAct2d via
@@ -270,10 +270,10 @@ int gemm_precision();   // api.cpp: process-wide compute precision of the engine
 // (wave-uniform) so the 16 x TM x TN stores of a lane are straight-line code, not a branch + wait per element.
 template <int TM, int TN>
 __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[TM][TN], const GemmEpi& ep, int M, int N, int i0, int j0, int BM, int BN,
-                                              int wm0, int wn0, int z) {
+                                              int wm0, int wn0, int z, long coff = 0) {      // coff: this k-slice's slab (GemmEpi::sk_stride), 0 otherwise
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
     const long cz = (long)(z / ep.inner) * ep.sc_outer + (long)(z % ep.inner) * ep.sc_inner;
-    float* C = ep.C + cz;
+    float* C = ep.C + cz + coff;
     const float* res = ep.res ? ep.res + cz : nullptr;
     const float* bias = ep.bias ? ep.bias + (long)z * ep.sbias : nullptr;
     const bool full = (i0 + BM <= M) && (j0 + BN <= N);
@@ -361,10 +361,10 @@ __device__ __forceinline__ void gemm_epilogue(const f32x16 (&acc)[TM][TN], const
 // i.e. four runs of 4 consecutive columns - 4 x 16-byte stores per lane instead of 16 x 4-byte ones (residual / mask / bias / accumulator reads
 // likewise).  Per element the same operations in the same order as gemm_epilogue.  Modes 0 / 1 only; the host guarantees N % 4 == 0 and the
 // 16-byte alignment of every row segment touched (epi16_eligible), so a 4-column group is inside the matrix or outside it as a whole.
-__device__ __forceinline__ void gemm_epilogue_t(const f32x16& acc, const GemmEpi& ep, int M, int N, int i0, int j0, int wm0, int wn0, int z) {
+__device__ __forceinline__ void gemm_epilogue_t(const f32x16& acc, const GemmEpi& ep, int M, int N, int i0, int j0, int wm0, int wn0, int z, long coff = 0) {
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
     const long cz = (long)(z / ep.inner) * ep.sc_outer + (long)(z % ep.inner) * ep.sc_inner;
-    float* C = ep.C + cz;
+    float* C = ep.C + cz + coff;
     const float* res = ep.res ? ep.res + cz : nullptr;
     const float* bias = ep.bias ? ep.bias + (long)z * ep.sbias : nullptr;
     if (ep.prec & 0x100) return;
@@ -413,7 +413,9 @@ __device__ __forceinline__ void gemm_epilogue_t(const f32x16& acc, const GemmEpi
 }
 
 // ---------------------------------------------------------------- kernel
-template <int BM, int BN, int WAVES_M, int BK, class LA, bool A_KC, class LB, bool B_KC, bool ALLVEC, int NT = 256, int PF = 1>
+// SLAB: the instantiation of the ordered slab k-split (gemm_slab_kernel; deterministic mode): k-slice blk_y stores its partial tile at C + blk_y * sk_stride.
+// A separate instantiation, so the kernels of the default mode are instruction for instruction what they were without it.
+template <int BM, int BN, int WAVES_M, int BK, class LA, bool A_KC, class LB, bool B_KC, bool ALLVEC, int NT = 256, int PF = 1, bool SLAB = false>
 __device__ __forceinline__ void gemm_tile(LA& la, LB& lb, const GemmEpi& ep, int M, int N, int K, int tiles_m, int tiles_n, int kchunk,
                                           float (*As)[BK][BM + GEMM_PAD], float (*Bs)[BK][BN + GEMM_PAD], int blk_x, int blk_y, int blk_z) {
     constexpr int WAVES_N = (NT / 64) / WAVES_M;
@@ -777,6 +779,14 @@ __device__ __forceinline__ void gemm_tile(LA& la, LB& lb, const GemmEpi& ep, int
         }
     }
 
+    if constexpr (SLAB) {
+        const long sko = (long)blk_y * ep.sk_stride;
+        if constexpr (TRN_OK) {
+            if (trn) { gemm_epilogue_t(acc[0][0], ep, M, N, i0, j0, wm0, wn0, z, sko); return; }
+        }
+        gemm_epilogue<TM, TN>(acc, ep, M, N, i0, j0, BM, BN, wm0, wn0, z, sko);
+        return;
+    }
     if constexpr (TRN_OK) {
         if (trn) { gemm_epilogue_t(acc[0][0], ep, M, N, i0, j0, wm0, wn0, z); return; }
     }
@@ -793,6 +803,14 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 2 : ((BM * BN >= 128 * 96) ? 3
     __shared__ __attribute__((aligned(16))) float As[2][BK][BM + GEMM_PAD];
     __shared__ __attribute__((aligned(16))) float Bs[2][BK][BN + GEMM_PAD];
     gemm_tile<BM, BN, WAVES_M, BK, LA, A_KC, LB, B_KC, ALLVEC, NT, PF>(la, lb, ep, M, N, K, tiles_m, tiles_n, kchunk, As, Bs, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// the ordered slab k-split of the deterministic mode (weight-gradient layouts only: see launch_cfg)
+template <int BM, int BN, int WAVES_M, int BK, class LA, bool A_KC, class LB, bool B_KC, bool ALLVEC, int NT = 256, int PF = 1>
+__global__ void __launch_bounds__(NT, NT == 512 ? 2 : ((BM * BN >= 128 * 96) ? 3 : 4)) gemm_slab_kernel(LA la, LB lb, GemmEpi ep, int M, int N, int K, int tiles_m, int tiles_n, int kchunk) {
+    __shared__ __attribute__((aligned(16))) float As[2][BK][BM + GEMM_PAD];
+    __shared__ __attribute__((aligned(16))) float Bs[2][BK][BN + GEMM_PAD];
+    gemm_tile<BM, BN, WAVES_M, BK, LA, A_KC, LB, B_KC, ALLVEC, NT, PF, true>(la, lb, ep, M, N, K, tiles_m, tiles_n, kchunk, As, Bs, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // ---------------------------------------------------------------- pair launch
@@ -866,8 +884,23 @@ inline int streamk_blocks(const GemmEpi& ep, int M, int N, int K, int batch, int
 constexpr int kTwoPass = 1000000;  // GemmPlan.splitk >= kTwoPass: two-pass split-K with S = splitk - kTwoPass slices (LDS-DMA kinds only); atomic split counts stay far below
 inline int twopass_ldws(int N) { return (N + 3) & ~3; }
 // eligibility of the two-pass split for this call: plain row-major single-batch output and enough caller scratch for S slices
-inline bool twopass_ok(const GemmEpi& ep, int M, int N, int batch, int S) {
-    return ep.sk_ws && batch == 1 && ep.ldcj == 1 && (ep.mode == 0 || ep.mode == 1) && S >= 2 && S <= 4 && (long)S * M * twopass_ldws(N) <= ep.sk_ws_floats;
+// (smax: the tuned two-pass plans stop at 4 slices; the ordered slab split of the deterministic mode keeps the slice count of the atomic plan it replaces)
+inline bool twopass_ok(const GemmEpi& ep, int M, int N, int batch, int S, int smax = 4) {
+    return ep.sk_ws && batch == 1 && ep.ldcj == 1 && (ep.mode == 0 || ep.mode == 1) && S >= 2 && S <= smax && (long)S * M * twopass_ldws(N) <= ep.sk_ws_floats;
+}
+// Deterministic mode (tf_set_deterministic): k-slices of the ORDERED SLAB split that replaces a plan's atomic k-split - slice s stores its raw
+// partial tile at sk_ws + s * M * ldws with plain stores, launch_splitk_fixup adds the slices to C in slice order.  The plan's own slice count,
+// lowered until the caller's scratch holds that many slices; 1 (unsplit) without scratch, for batched calls and column-strided outputs.
+constexpr int kSlabMax = 1 << 16;
+// the register-staged slab kernels (gemm_slab_kernel) are instantiated for the weight-gradient layouts only - both operands stored with the contraction
+// index as their row ([tn] GEMMs, the implicit-GEMM convolution weight gradients): every k-split plan of the train step has this layout; an
+// accumulating call of another layout runs unsplit in the deterministic mode
+template <bool A_KC, bool B_KC> constexpr bool kSlabLayout = !A_KC && !B_KC;
+inline int slab_slices(const GemmEpi& ep, int M, int N, int batch, int splitk) {
+    if (!ep.sk_ws || batch != 1 || ep.ldcj != 1 || ep.mode != 1 || splitk < 2) return 1;
+    const long fit = ep.sk_ws_floats / ((long)M * twopass_ldws(N));
+    const long S = splitk < fit ? splitk : fit;
+    return S < 2 ? 1 : (int)(S < kSlabMax ? S : kSlabMax);
 }
 
 // pair launch (gemm_pair.cpp): between tf_gemm_pair_begin() and tf_gemm_pair_end() up to two eligible GEMMs are held back and launched as ONE grid
@@ -907,6 +940,17 @@ inline GemmPlan plan_gemm(int M, int N, int K, int batch, bool allow_splitk) {
     if ((p.bn == 128 || p.bn == 64) && t128 < 384 && M > 64) p.bm = 64;
     p.splitk = allow_splitk ? heuristic_splitk(M, N, K, batch, p.bm, p.bn, p.bk) : 1;
     return p;
+}
+
+// Deterministic mode: scratch floats the ordered slab k-split of a pure accumulation (batch 1, row-major output) at site `what` wants - the plan
+// launch_gemm will pick for it under the flag (pinned, cached or heuristic: never tuned) times one [M][ldws] slice per k-slice; 0 = the plan does
+// not split K atomically.
+inline long slab_ws_floats(const char* what, int M, int N, int K) {
+    GemmPlan p;
+    const int acc = 2 + 4 * (gemm_precision() == 3 ? 1 : gemm_precision());
+    if (!forced_plan(&p) && !plan_lookup(what, M, N, K, 1, acc, &p)) p = plan_gemm(M, N, K, 1, true);
+    if (p.splitk < 2 || p.splitk >= kTwoPass) return 0;
+    return (long)(p.splitk < kSlabMax ? p.splitk : kSlabMax) * M * twopass_ldws(N);
 }
 
 // 16-byte epilogue on a transposed accumulator (GemmEpi::trn, gemm_epilogue_t).  TF_GEMM_EPI16=0 keeps every launch on the 4-byte epilogue.
@@ -952,15 +996,34 @@ inline CfgGeom cfg_geom(const GemmEpi& ep, int M, int N, int K, int splitk, int 
     if (c.epg.stat_nparts) *c.epg.stat_nparts = c.epg.stat ? cdiv(M, BM / WAVES_M) : 0;
     c.epg.trn = epi16_eligible(c.epg, N, BM, BN, WAVES_M, allvec) ? 1 : 0;
     if (c.epg.trn) epi16_count(1);
+    if (c.epg.mode == 2) float_atomic_count(1);
     return c;
 }
 
 template <int BM, int BN, int WAVES_M, int BK, class LA, bool A_KC, class LB, bool B_KC, int NT = 256, int PF = 1>
-inline void launch_cfg(const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, int splitk, void* stream) {
-    const CfgGeom cg = cfg_geom(ep, M, N, K, splitk, BM, BN, BK, WAVES_M, la.vec && lb.vec);
+inline void launch_cfg(const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, int splitk, void* stream, bool slab = false) {
+    GemmEpi eps = ep;
+    const int ldws = twopass_ldws(N);
+    slab = slab && kSlabLayout<A_KC, B_KC>;
+    if (slab) {         // ordered slab k-split (batch 1): the slices store raw partial sums [M][ldws] into the caller's scratch, the epilogue proper runs in the fix-up pass
+        eps.C = ep.sk_ws; eps.ldc = ldws; eps.ldcj = 1; eps.sc_outer = eps.sc_inner = 0; eps.inner = 1; eps.bias = nullptr; eps.res = nullptr;
+        eps.mask = nullptr; eps.alpha = 1.f; eps.relu = 0; eps.mode = 0; eps.sk_stride = (long)M * ldws;
+        eps.drop_seed = nullptr; eps.stat = nullptr; eps.stat_nparts = nullptr;
+    }
+    const CfgGeom cg = cfg_geom(eps, M, N, K, splitk, BM, BN, BK, WAVES_M, la.vec && lb.vec);
     const int tiles_m = cg.tiles_m, tiles_n = cg.tiles_n, kchunk = cg.kchunk;
     dim3 grid(tiles_m * tiles_n, cg.nsplit, batch);
     const GemmEpi& epg = cg.epg;
+    if constexpr (kSlabLayout<A_KC, B_KC>) {
+        if (slab) {
+            if (la.vec && lb.vec)
+                TF_LAUNCH((gemm_slab_kernel<BM, BN, WAVES_M, BK, LA, A_KC, LB, B_KC, true, NT, PF>), grid, dim3(NT), stream, la, lb, epg, M, N, K, tiles_m, tiles_n, kchunk);
+            else
+                TF_LAUNCH((gemm_slab_kernel<BM, BN, WAVES_M, BK, LA, A_KC, LB, B_KC, false, NT, PF>), grid, dim3(NT), stream, la, lb, epg, M, N, K, tiles_m, tiles_n, kchunk);
+            launch_splitk_fixup(ep.sk_ws, cg.nsplit, (long)M * ldws, ldws, ep, M, N, stream);
+            return;
+        }
+    }
     if (la.vec && lb.vec)
         TF_LAUNCH((gemm_kernel<BM, BN, WAVES_M, BK, LA, A_KC, LB, B_KC, true, NT, PF>), grid, dim3(NT), stream, la, lb, epg, M, N, K, tiles_m, tiles_n, kchunk);
     else
@@ -968,18 +1031,19 @@ inline void launch_cfg(const LA& la, const LB& lb, const GemmEpi& ep, int M, int
 }
 
 template <class LA, bool A_KC, class LB, bool B_KC>
-inline void launch_plan(const GemmPlan& p, const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, void* stream) {
+inline void launch_plan(const GemmPlan& p, const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, void* stream, int slab = 0) {
+    // slab >= 2: the ordered slab k-split of the deterministic mode with that many slices (slab_slices): the LDS-DMA kernels run it as their two-pass split
     if constexpr (std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value) {
         if (p.kind >= 1 && p.kind <= kDmaKinds && dma_eligible(la, lb)) {
-            launch_dma_plan<A_KC, B_KC>(p.kind, la, lb, ep, M, N, K, batch, p.splitk, stream);
+            launch_dma_plan<A_KC, B_KC>(p.kind, la, lb, ep, M, N, K, batch, slab ? kTwoPass + slab : p.splitk, stream);
             return;
         }
     }
-    const int sk = p.splitk >= kTwoPass ? 1 : p.splitk;       // the two-pass split exists in the LDS-DMA kernels only
+    const int sk = slab ? slab : (p.splitk >= kTwoPass ? 1 : p.splitk);       // the tuned two-pass plans exist in the LDS-DMA kernels only
 #define TF_CFG(BM_, BN_, WM_)                                                                                      \
     do {                                                                                                           \
-        if (p.bk == 32) launch_cfg<BM_, BN_, WM_, 32, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk, stream); \
-        else launch_cfg<BM_, BN_, WM_, 16, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk, stream);       \
+        if (p.bk == 32) launch_cfg<BM_, BN_, WM_, 32, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk, stream, slab != 0); \
+        else launch_cfg<BM_, BN_, WM_, 16, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk, stream, slab != 0);       \
     } while (0)
     if (p.bm == 128) {
         if (p.bn == 32) TF_CFG(128, 32, 4);
@@ -1113,12 +1177,13 @@ inline int launch_gemm(const LA& la, const LB& lb, GemmEpi ep, int M, int N, int
     // split-K only for pure accumulations (weight gradients into the grad arena): atomic epilogue
     const bool sk_ok = allow_splitk && ep.mode == 1 && !ep.bias && !ep.res && !ep.relu;
     const int acc = (ep.mode != 0 ? (sk_ok ? 2 : 1) : 0) + 4 * (gemm_precision() == 3 ? 1 : gemm_precision());   // plans are tuned per compute precision (fp16 shares the bf16 plans)
+    const bool det = deterministic();     // tf_set_deterministic: no atomic k-split, no tuning (the plan cache records nothing found under the flag)
     GemmPlan p;
     if (forced_plan(&p)) {
         if (!sk_ok && p.splitk < kTwoPass) p.splitk = 1;
     } else if (!plan_lookup(what, M, N, K, batch, acc, &p)) {
 #ifndef TF_EMU
-        if (autotune_enabled()) {
+        if (autotune_enabled() && !det) {
             p = autotune_gemm<LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk_ok, stream);
             plan_store(what, M, N, K, batch, acc, p);
         } else
@@ -1145,21 +1210,26 @@ inline int launch_gemm(const LA& la, const LB& lb, GemmEpi ep, int M, int N, int
         if (ep.mode != 0 || ep.res || ep.relu || ep.mask) ep.stat = nullptr;
         if (!ep.stat && ep.stat_nparts) *ep.stat_nparts = 0;
     }
+    int slab = 0;
     if (streamk) {
     } else if (p.splitk >= kTwoPass) {
         if (p.kind < 1 || !twopass_ok(ep, M, N, batch, p.splitk - kTwoPass)) p.splitk = 1;     // no scratch on this call / not a plain output
     } else {
         if (!sk_ok) p.splitk = 1;
-        if (p.splitk > 1) ep.mode = 2;
+        if (p.splitk > 1 && det) {          // the plan's tile and slice count, the slices combined in slice order through the caller's scratch
+            slab = kSlabLayout<A_KC, B_KC> ? slab_slices(ep, M, N, batch, p.splitk) : 1;
+            if (slab < 2) { slab = 0; p.splitk = 1; }
+            else slab_splitk_count(1);
+        } else if (p.splitk > 1) ep.mode = 2;
     }
     if constexpr (std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value) {
         // tf_gemm_pair_begin(): a 64 x 64-tile register-staged launch with vector operands is held back so that tf_gemm_pair_end() can put
         // it into one grid with its partner (gemm_pair.cpp); anything else launches right here, as always
-        if (pair_capturing() && p.kind == 0 && p.bm == 64 && p.bn == 64 && (p.bk == 16 || p.bk == 32) && p.splitk < kTwoPass && batch == 1 && la.vec && lb.vec &&
+        if (!det && pair_capturing() && p.kind == 0 && p.bm == 64 && p.bn == 64 && (p.bk == 16 || p.bk == 32) && p.splitk < kTwoPass && batch == 1 && la.vec && lb.vec &&
             !ep.stat && pair_hold(la, lb, ep, M, N, K, A_KC, B_KC, p, what))
             return 0;
     }
-    launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, ep, M, N, K, batch, stream);
+    launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, ep, M, N, K, batch, stream, slab);
     return launch_status(what);
 }
 

@@ -288,6 +288,9 @@ __device__ __forceinline__ void mfma_32x32x16_x3(const float (&a)[8], const floa
     mfma_x3_presplit(split_bf16x3(a), split_bf16x3(b), acc);
 }
 
+// one row's term of the LayerNorm weight gradient dgamma[c] = sum_rows dy xhat (norm.cpp: the atomic form, reduce.cpp: the fixed-order form)
+__device__ __forceinline__ float ln_dgamma_term(float dy, float x, float mean, float rstd) { return dy * ((x - mean) * rstd); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += shfl_xor(v, m);

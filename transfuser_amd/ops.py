@@ -108,6 +108,54 @@ def get_precision():
     return ("fp32", "bf16", "f32x3", "fp16")[L().tf_get_precision()]
 
 
+# ---- deterministic mode (csrc/api.cpp: tf_set_deterministic) ------------------------------------------------------------------------------
+# By default several reductions of a train step end in fp32 atomics (the k-split weight gradients of the MFMA engine, the grouped 3x3 weight
+# gradient, LayerNorm dgamma / dbeta, the SE excitation backward, the small-M input gradient, the skinny head weight gradients), so two identical
+# steps differ in the last bits.  With the flag on each of them takes a fixed-order form through caller scratch (allocated right here, from the
+# caching allocator, per call), and what has no such form raises instead of running atomics (dwconv7_wgrad).  The flag is process-wide and read by
+# the library when a call is ISSUED: a captured graph keeps the forms it was captured with.  TF_DETERMINISTIC=1 sets the initial value.
+_det = [None]      # the library's flag as last seen from here (None: not asked yet)
+
+
+def is_deterministic():
+    if _det[0] is None:
+        _det[0] = bool(L().tf_get_deterministic())
+    return _det[0]
+
+
+def set_deterministic(on):
+    check(L().tf_set_deterministic(int(bool(on))), "tf_set_deterministic")
+    _det[0] = bool(on)
+
+
+class deterministic:
+    """with ops.deterministic(on=True): ...   (restores the previous value)"""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = is_deterministic()
+        set_deterministic(self.on)
+        return self
+
+    def __exit__(self, *a):
+        set_deterministic(self.prev)
+        return False
+
+
+def float_atomic_launches():
+    """Launches so far of kernel forms that combine partial results with float atomics (stands still while the deterministic mode is on)."""
+    L().tf_float_atomic_launches.restype = ctypes.c_long
+    return L().tf_float_atomic_launches()
+
+
+def slab_splitk_launches():
+    """Launches so far of the engine's ordered slab k-split (the deterministic mode's replacement of the atomic k-split)."""
+    L().tf_slab_splitk_launches.restype = ctypes.c_long
+    return L().tf_slab_splitk_launches()
+
+
 # ---- 16-bit operand storage (csrc/cast16.cpp, tf_gemm16_nt_f32)
 _STORE16 = os.environ.get("TF_STORE16", "1") != "0"
 _lowp = {"dtype": 0, "managed": False, "w": {}}
@@ -445,7 +493,9 @@ def gemm(a, b, c, m, n, k, lda, ldb, ldc, a_trans=False, b_trans=False, bias=Non
         assert ldc == n and batch == 1 and not accumulate, "gemm: dropout epilogue needs a contiguous (m, n) plain store"
         d.drop_seed, d.drop_site, d.drop_p = ptr(drop[0]), int(drop[1]), float(drop[2])
     skws = None
-    if TWO_PASS_SPLITK and batch == 1 and k >= 256 and 128 * 128 <= m * n and (m * n <= _TWO_PASS_MAX_ELEMS or STREAM_K):
+    # (deterministic mode: every accumulating call asks - the ordered slab k-split / the skinny weight gradient take their partials from this scratch)
+    if batch == 1 and ((accumulate and is_deterministic()) or
+                       (TWO_PASS_SPLITK and k >= 256 and 128 * 128 <= m * n and (m * n <= _TWO_PASS_MAX_ELEMS or STREAM_K))):
         need = _ws_query()(byref(d))          # > 0 only when the plan of THIS shape is a two-pass / stream-K plan (or the autotuner wants to try one)
         if need > 0:
             skws = torch.empty(need, dtype=torch.float32, device=c.device)
@@ -751,7 +801,14 @@ def _conv_wgrad(dy, x, dw, stride, pad, groups, accumulate, dbias):
                                                   stream_of(dy)), "tf_conv3x3_grouped_s2_wgrad_f32")
         _census_end(_e, "conv wgrad g2", _gshape(g), _gflops(g))
         return dw
-    check(L().tf_conv2d_wgrad_f32(byref(g), ptr(_c(dy)), ptr(_c(x)), wptr(dw), int(accumulate), stream_of(dy)), "tf_conv2d_wgrad_f32")
+    if is_deterministic():      # the k-slices of the weight gradient go through scratch of ours and are added in slice order
+        L().tf_conv2d_wgrad_ws_floats.restype = ctypes.c_long
+        need = L().tf_conv2d_wgrad_ws_floats(byref(g)) if accumulate else 0
+        ws = torch.empty(need, dtype=torch.float32, device=dy.device) if need > 0 else None
+        check(L().tf_conv2d_wgrad_ws_f32(byref(g), ptr(_c(dy)), ptr(_c(x)), wptr(dw), int(accumulate), ptr(ws), ctypes.c_long(need), stream_of(dy)),
+              "tf_conv2d_wgrad_ws_f32")
+    else:
+        check(L().tf_conv2d_wgrad_f32(byref(g), ptr(_c(dy)), ptr(_c(x)), wptr(dw), int(accumulate), stream_of(dy)), "tf_conv2d_wgrad_f32")
     _census_end(_e, "conv wgrad", _gshape(g), _gflops(g))
     return dw
 
@@ -887,6 +944,11 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma=None, dbeta=None, dx=None, ac
     rows, C = x.shape
     if dx is None:
         dx = torch.empty_like(x)
+    if is_deterministic() and dgamma is not None and dbeta is not None:
+        # dgamma / dbeta in fixed summation order by a launch of their own (chunk partials in the reduction workspace); the fused entry gets none
+        check(L().tf_layernorm_bwd_dw_f32(ptr(_c(dy)), ptr(_c(x)), ptr(mean), ptr(rstd), ptr(dgamma), ptr(dbeta), rows, C, ptr(workspace(x.device)), stream_of(x)),
+              "tf_layernorm_bwd_dw_f32")
+        dgamma = dbeta = None
     if drop is not None:
         dropped = torch.empty_like(dx)
         assert dx.is_contiguous()
@@ -1116,6 +1178,20 @@ def se_scale_bn_fwd(y, coef, gate):
     return out
 
 
+def _se_bwd_scratch(g1, B, C, Cr):
+    """(scratch, is_zero) of an SE excitation backward: the (B, Cr) accumulator the forward cleared (valid for ONE backward), or - deterministic
+    mode - one (B, Cr) slab per block of the fc2 pass (tf_se_excite_bwd_ws_floats)."""
+    if is_deterministic():
+        L().tf_se_excite_bwd_ws_floats.restype = ctypes.c_long
+        g1._bwd_scratch = None
+        return torch.empty(L().tf_se_excite_bwd_ws_floats(B, C, Cr), dtype=torch.float32, device=g1.device), False
+    scratch = getattr(g1, "_bwd_scratch", None)
+    if scratch is not None:
+        g1._bwd_scratch = None
+        return scratch, True
+    return torch.empty(B, Cr, dtype=torch.float32, device=g1.device), False
+
+
 def se_gate_excite_bn_bwd(dz2s, y, coef, gate, s, g1, w1, w2, dw1, db1, dw2, db2):
     """Backward of the excitation fed by the gate gradient sum_hw dz2s * relu(y * scale + shift) (chunk sums finished inside the fc2 kernel);
     accumulates the four parameter gradients, returns ds (B, C)."""
@@ -1125,12 +1201,7 @@ def se_gate_excite_bn_bwd(dz2s, y, coef, gate, s, g1, w1, w2, dw1, db1, dw2, db2
     ws = workspace(y.device)
     check(L().tf_se_gate_grad_parts_f32(ptr(_c(dz2s)), ptr(_c(y)), ptr(coef), B, H * W, C, ptr(ws), byref(nch), stream_of(y)), "tf_se_gate_grad_parts_f32")
     ds = torch.empty(B, C, dtype=torch.float32, device=y.device)
-    scratch = getattr(g1, "_bwd_scratch", None)
-    zeroed = scratch is not None
-    if zeroed:
-        g1._bwd_scratch = None
-    else:
-        scratch = torch.empty(B, Cr, dtype=torch.float32, device=y.device)
+    scratch, zeroed = _se_bwd_scratch(g1, B, C, Cr)
     check(L().tf_se_excite_bwd_parts_f32(ptr(ws), nch.value, ptr(_c(gate)), ptr(_c(s)), ptr(_c(g1)), wptr(w1), wptr(w2), B, C, Cr, wptr(dw1), ptr(db1), wptr(dw2),
                                          ptr(db2), ptr(ds), ptr(scratch), int(zeroed), stream_of(y)), "tf_se_excite_bwd_parts_f32")
     return ds
@@ -1255,12 +1326,7 @@ def se_excite_bwd(dgate, s, g1, w1, w2, dw1, db1, dw2, db2):
     B, C = s.shape
     Cr = w1.shape[0]
     ds = torch.empty(B, C, dtype=torch.float32, device=s.device)
-    scratch = getattr(g1, "_bwd_scratch", None)      # cleared by se_excite_fwd; valid for ONE backward
-    zeroed = scratch is not None
-    if zeroed:
-        g1._bwd_scratch = None
-    else:
-        scratch = torch.empty(B, Cr, dtype=torch.float32, device=s.device)
+    scratch, zeroed = _se_bwd_scratch(g1, B, C, Cr)
     check(L().tf_se_excite_bwd_f32(ptr(_c(dgate)), ptr(_c(s)), ptr(_c(g1)), wptr(w1), wptr(w2), B, C, Cr, wptr(dw1), ptr(db1), wptr(dw2), ptr(db2),
                                    ptr(ds), ptr(scratch), int(zeroed), stream_of(s)), "tf_se_excite_bwd_f32")
     return ds

@@ -389,7 +389,7 @@ class Engine:
     DEFAULT_CUTS = ((4, 1, 3), (4, 1, 2), (4, 1, 1), 3, (3, 0, 0), 2, 1)
 
     def __init__(self, model, config, lr=1e-4, use_graph=False, group=None, bucket_mb=64.0, wp_only=False, autotune=True, plan_file=None,
-                 zero_redundancy_optimizer=False, sync_batch_norm=False, cuts=None, precision=None, grad_dtype="fp32", loss_scale=None):
+                 zero_redundancy_optimizer=False, sync_batch_norm=False, cuts=None, precision=None, grad_dtype="fp32", loss_scale=None, deterministic=None):
         """``cuts``: points (cut_key: int c = after fusion stage c; (i, 0, 0) = between the stage-i trunks and GPT i; (i, 1, j) = inside GPT i
         in front of Block j) at which the backward is cut into separately enqueued (and separately captured) segments whose gradient
         ranges are all-reduced while the next segment runs.  None = DEFAULT_CUTS when there is more than one rank (and the backbone is a
@@ -399,9 +399,17 @@ class Engine:
         None = 1 in the fp32 / f32x3 / bf16 modes and a DYNAMIC scale in fp16 mode (initial 2^16, device-side overflow check in front of
         AdamW: the step is skipped and the scale halved on Inf / NaN gradients, doubled after ``loss_scale_growth_interval`` = 2000 clean
         steps - torch.cuda.amp.GradScaler's policy; the reference trains fp32 and has no counterpart); formerly None = static 1024
-        in "fp16" precision (half operands flush gradients below 6e-8 to zero) and 1 otherwise.  The reported losses are unscaled."""
+        in "fp16" precision (half operands flush gradients below 6e-8 to zero) and 1 otherwise.  The reported losses are unscaled.
+        ``deterministic``: None keeps the process-wide flag (ops.set_deterministic, TF_DETERMINISTIC), True / False sets it here, before anything is
+        tuned or captured.  On, in "fp32" precision on one GPU, every forward output, loss, gradient and AdamW-updated parameter of a train step is a
+        pure function of (inputs, parameters, dropout seed, GEMM plans): bitwise equal run to run, and across processes that load the same plan file
+        with ``autotune=False`` (nothing is tuned under the flag).  The flag is read when a kernel is ISSUED, so it is fixed into a captured graph at
+        capture time: flipping it afterwards changes eager calls only.  Other precisions (their stored-operand kernels are not audited) and more
+        than one rank (the all-reduce order is RCCL's) raise NotImplementedError."""
         self.model = model
         self.config = config
+        if deterministic is not None and (next(model.parameters()).is_cuda or ops._lib.is_test_backend()):
+            ops.set_deterministic(deterministic)
         if precision is not None:   # "fp32" (exact fp32 MFMA: the reference's arithmetic) | "f32x3" (bf16x3 split on the bf16 MFMA, fp32-accurate) | "bf16" (bf16 MFMA operands, fp32 accumulate / storage / master weights)
             ops.set_precision(precision)
         self._autotune_pending = bool(autotune) and next(model.parameters()).is_cuda
@@ -410,6 +418,11 @@ class Engine:
         if next(model.parameters()).is_cuda and os.path.exists(plan_file):
             ops.plans_load(plan_file)
         world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+        self.deterministic = ops.is_deterministic() if (next(model.parameters()).is_cuda or ops._lib.is_test_backend()) else bool(deterministic)
+        if self.deterministic and ops.get_precision() != "fp32":
+            raise NotImplementedError("deterministic mode is audited for precision 'fp32' only (got %r): the 16-bit / f32x3 kernels keep their atomic reductions" % ops.get_precision())
+        if self.deterministic and world > 1:
+            raise NotImplementedError("deterministic mode covers one GPU: the summation order of the gradient all-reduce over %d ranks is the collective library's" % world)
         if sync_batch_norm and world > 1:   # train.py:132-133
             from .functions import convert_sync_batchnorm
             convert_sync_batchnorm(model, group)
@@ -775,6 +788,7 @@ def build_parser():
     # additions of this framework
     p.add_argument('--use_graph', type=int, default=1, help='capture the step into hipGraphs (falls back to eager where a flag requires it)')
     p.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'f32x3', 'bf16'])
+    p.add_argument('--deterministic', type=int, default=0, help='1: bitwise-reproducible fp32 train step on one GPU (fixed-order reductions instead of fp32 atomics; Engine(deterministic=True))')
     p.add_argument('--height', type=int, default=160, help="RGB height of the synthetic samples (the dataset's crop is 160 x 704)")
     p.add_argument('--num_workers', type=int, default=None)
     p.add_argument('--width', type=int, default=704)
@@ -813,7 +827,8 @@ def main(argv=None):
     if args.load_file is not None:      # train.py:180-183 (accepts checkpoints with or without DDP's 'module.' prefix)
         model.load_reference_checkpoint(args.load_file) if hasattr(model, "load_reference_checkpoint") else model.load_state_dict(torch.load(args.load_file, map_location=device))
     eng = Engine(model, config, lr=args.lr, use_graph=bool(args.use_graph) and cuda, wp_only=bool(args.wp_only),
-                 zero_redundancy_optimizer=bool(args.zero_redundancy_optimizer), sync_batch_norm=bool(args.sync_batch_norm), precision=args.precision if cuda else None)
+                 zero_redundancy_optimizer=bool(args.zero_redundancy_optimizer), sync_batch_norm=bool(args.sync_batch_norm), precision=args.precision if cuda else None,
+                 deterministic=True if (args.deterministic and cuda) else None)
     if args.load_file is not None and os.path.exists(args.load_file.replace("model_", "optimizer_")):
         eng.optimizer.load_state_dict(torch.load(args.load_file.replace("model_", "optimizer_"), map_location=device))
     shared_dict = None
