@@ -65,6 +65,11 @@ long tf_slab_splitk_launches(void);
 int tf_set_precision(int mode);
 int tf_get_precision(void);
 int tf_autotune(int enable);
+/* The integer `splitk` of tf_force_plan / tf_force_dma and of the 10th field of a plan file (tf_plans_load / tf_plans_save) encodes how the
+ * plan partitions K: 1 = no k-split; 2 .. 999999 = that many k-slices added into C with fp32 atomics (pure accumulations only; under
+ * tf_set_deterministic(1) the same slices through the ordered slab split); 1000000 + S = two-pass split with S = 2..4 slices through
+ * tf_gemm_desc.splitk_ws (LDS-DMA configurations only); 2000000 = stream-K (LDS-DMA configurations only; needs splitk_ws and sk_flags).  A call
+ * that cannot take its plan's partition runs unsplit.  Inside the library the encoding exists in one decode / encode pair (csrc/api.cpp). */
 int tf_force_plan(int bm, int bn, int bk, int splitk); /* tests: pin one tiling of the register-staged kernel (bm = 0 clears) */
 int tf_force_dma(int kind, int splitk);                /* tests: pin LDS-DMA configuration `kind` (1..8, tf_gemm_dma.h) for every eligible call */
 int tf_plans_count(void);

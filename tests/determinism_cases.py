@@ -4,6 +4,9 @@ and checks three things: the launch counters (tf_float_atomic_launches stands st
 counter is live), bitwise equality of repeated calls from identical inputs, and the value against a float64 CPU reference within the tolerance
 the site's existing kernel_cases.check_* applies (kernel_cases.close, TOL = 1e-3 of the reference's scale; 3e-5 for the skinny weight gradient).
 The emulator runs blocks sequentially, so there the cases pin indexing, ragged edges and scratch sizing rather than ordering."""
+import contextlib
+import ctypes
+
 import torch
 import torch.nn.functional as F
 
@@ -127,6 +130,103 @@ def check_engine_ksplit_conv(dev, B, Hi, Wi, Cin, Cout, ks, stride, groups, spli
         dw = run_det(dev, call, slab=(groups == 1))
         atomic_form_is_counted(call)
     close(dw, c64(dw0) + gw, what="slab k-split conv wgrad %s" % ((B, Hi, Wi, Cin, Cout, ks, stride, groups),))
+
+
+# ---------------------------------------------------------------- 2b. the scratch query agrees with the launch
+# pins of the engine plan; the two-pass / stream-K codes are kernel_cases.TWO_PASS / STREAM_K (include/transfuser_hip.h, tf_force_dma)
+QUERY_PINS = {"none": None, "reg3": ("reg4", 3), "dma3": ("dma", 3), "dma-twopass3": ("dma", kc.TWO_PASS + 3), "dma-streamk": ("dma", kc.STREAM_K)}
+QUERY_SITES = ("tn72", "tn12", "tn136", "conv24", "conv48", "stem7")
+
+
+def _query_site(dev, site):
+    """-> (query() -> floats, call(ws, floats) -> result, float64 reference, (m, n) of the engine's row-major output, plain operands?)."""
+    from ctypes import byref, c_long
+    from transfuser_amd.ops import ptr, wptr, stream_of, check, c_p
+    L = ops.L()
+    if site.startswith("tn"):          # plain [tn] accumulation, k = 1030; m = 12 is the shape whose default orientation is swapped; 136 x 136: 9 tiles of 64 x 64 (a cut stream-K launch)
+        m, n, k = int(site[2:]), (136 if site == "tn136" else 96), 1030
+        dy, x, dw0 = R(k, m, dev=dev), R(k, n, seed=1, dev=dev), R(m, n, seed=2, dev=dev)
+        flags = ops._sk_flags(dy.device)
+
+        def desc(dw, ws, floats):
+            return ops.GemmDesc(a=ptr(dy), b=ptr(x), c=ptr(dw), bias=c_p(0), res=c_p(0), m=m, n=n, k=k, a_trans=1, b_trans=1, lda=m, ldb=n, ldc=n, ldres=0, batch=1,
+                                inner=1, alpha=1.0, relu=0, accumulate=1, mask=c_p(0), ldmask=0, splitk_ws=ptr(ws), splitk_ws_floats=floats, sk_flags=ptr(flags))
+
+        def call(ws, floats):
+            dw = dw0.clone()
+            check(L.tf_gemm_f32(byref(desc(dw, ws, floats)), stream_of(dy)), "tf_gemm_f32")
+            assert not flags.any(), "stream-K flags must be clear between launches"
+            return dw
+        return (lambda: ops._ws_query()(byref(desc(dw0, None, 0)))), call, c64(dw0) + c64(dy).t() @ c64(x), (m, n), True
+    if site.startswith("conv"):        # one-group 3x3 convolution weight gradient; Cout = 24 is swapped by default
+        B, H, W, Cin, Cout = 2, 6, 10, 8, int(site[4:])
+        x = R(B, Cin, H, W, dev="cpu")
+        w64 = (c64(R(Cout, Cin, 3, 3, dev="cpu")) * 0.1).requires_grad_(True)
+        y = F.conv2d(c64(x), w64, None, 1, 1)
+        dy = R(*y.shape, seed=1, dev="cpu")
+        (gw,) = torch.autograd.grad(y, [w64], c64(dy))
+        xh, dyh = x.permute(0, 2, 3, 1).contiguous().to(dev), dy.permute(0, 2, 3, 1).contiguous().to(dev)
+        dw0 = kc.cl(R(Cout, Cin, 3, 3, seed=2, dev="cpu")).to(dev)
+        g = ops.conv_geom(xh.shape, Cout, 3, 1, 1, 1)
+        L.tf_conv2d_wgrad_ws_floats.restype = c_long
+
+        def call(ws, floats):
+            dw = dw0.clone(memory_format=torch.preserve_format)
+            check(L.tf_conv2d_wgrad_ws_f32(byref(g), ptr(dyh), ptr(xh), wptr(dw), 1, ptr(ws), c_long(floats), stream_of(dyh)), "tf_conv2d_wgrad_ws_f32")
+            return dw
+        return (lambda: L.tf_conv2d_wgrad_ws_floats(byref(g))), call, c64(dw0) + gw, (Cout, 9 * Cin), False
+    # the 7x7 / stride 2 stem weight gradient: ops.stem_conv_wgrad asks tf_stem_conv_wgrad_ws_floats and brings exactly that
+    rgb = torch.randint(0, 256, (2, 3, 32, 32), generator=torch.Generator().manual_seed(0)).float().to(dev)
+    w64 = (c64(R(16, 3, 7, 7, dev=dev)) * 0.1).requires_grad_(True)
+    mean, std = c64(torch.tensor([0.485, 0.456, 0.406], device=dev)).view(1, 3, 1, 1), c64(torch.tensor([0.229, 0.224, 0.225], device=dev)).view(1, 3, 1, 1)
+    y = F.conv2d((c64(rgb) / 255.0 - mean) / std, w64, None, 2, 3)
+    dy = R(*y.shape, seed=1, dev=dev)
+    (gw,) = torch.autograd.grad(y, [w64], c64(dy))
+    dyh, dw0 = dy.permute(0, 2, 3, 1).contiguous(), kc.cl(R(16, 3, 7, 7, seed=2, dev=dev))
+    g = ops.conv_geom((2, 32, 32, 3), 16, 7, 2, 3, 1)
+    L.tf_stem_conv_wgrad_ws_floats.restype = c_long
+    call = lambda ws, floats: ops.stem_conv_wgrad(dyh, rgb, None, dw0.clone(memory_format=torch.preserve_format), True, True, 2, 3)
+    return (lambda: L.tf_stem_conv_wgrad_ws_floats(byref(g), 3, 0)), call, c64(dw0) + gw, (16, 147), False
+
+
+def check_scratch_query_agrees(dev, site):
+    """Every pin of QUERY_PINS, flag on and off: ask the site's scratch query, make the call with EXACTLY that scratch, and read off the counters
+    that the launch took the form the answer implies (both come from resolve_plan, csrc/gemm_plan.cpp):
+    under the flag the float-atomic counter stands still, the slab counter moves exactly when an atomic-split plan (pinned or heuristic) was
+    answered with need > 0, and never with need == 0; a pinned stream-K plan runs as stream-K exactly when need > 0 (the 136 x 136 output is cut
+    on the 8 emulated CUs and on the MI355X alike, the 4-tile outputs never are); a pinned two-pass plan is answered with its 3 slices of
+    m * round_up(n, 4) for a row-major plain call and with 0 where the launch cannot take it (column-strided swapped orientation, implicit-GEMM
+    operands).  Results: bitwise equal run to run wherever no float atomics ran, and close (TOL) to the float64 product."""
+    query, call, want, (m, n), plain = _query_site(dev, site)
+    L = ops.L()
+    L.tf_streamk_launches.restype = ctypes.c_long
+    slice_floats = m * ((n + 3) // 4 * 4)
+    for pin, spec in QUERY_PINS.items():
+        for flag in (True, False):
+            with ops.deterministic(flag), (pinned(*spec) if spec else contextlib.nullcontext()):
+                need = query()
+                ws = torch.empty(need, dtype=torch.float32, device=dev) if need > 0 else None
+                outs = []
+                for _ in range(2):
+                    a0, s0, k0 = ops.float_atomic_launches(), ops.slab_splitk_launches(), L.tf_streamk_launches()
+                    outs.append(call(ws, need))
+                    atomic, slab, streamk = ops.float_atomic_launches() > a0, ops.slab_splitk_launches() > s0, L.tf_streamk_launches() > k0
+                    what = "%s pin %s flag %d: need %d atomic %d slab %d stream-K %d" % (site, pin, flag, need, atomic, slab, streamk)
+                    assert streamk == (pin == "dma-streamk" and need > 0), what
+                    if flag:
+                        assert not atomic, what
+                        assert slab == (need > 0 and pin in ("none", "reg3", "dma3")), what
+                    else:
+                        assert not slab, what
+                    if pin == "dma-twopass3":
+                        swapped = not flag and site in ("tn12", "conv24")
+                        assert need == (3 * slice_floats if plain and not swapped else 0), what
+                        assert not atomic and not slab, what
+                    if pin == "dma-streamk":
+                        assert (need > 0) == (site == "tn136"), what
+                if not atomic:
+                    assert torch.equal(outs[0], outs[1]), what + ": repeated calls differ"
+                close(outs[0], want, what=what)
 
 
 # ---------------------------------------------------------------- 3. the other sites

@@ -1777,7 +1777,7 @@ def check_f32x3_direct(dev):
 
 
 # ---------------------------------------------------------------- deterministic two-pass split-K (few-tile outputs, csrc/gemm_fixup.cpp)
-TWO_PASS = 1000000       # tf_gemm_engine.h kTwoPass: splitk = TWO_PASS + S
+TWO_PASS = 1000000       # splitk = TWO_PASS + S: two-pass split with S slices (the splitk encoding of include/transfuser_hip.h, at tf_force_plan / tf_force_dma)
 TWO_PASS_CASES = [(1, TWO_PASS + 2), (2, TWO_PASS + 3), (5, TWO_PASS + 4), (6, TWO_PASS + 3), (8, TWO_PASS + 2)]
 
 
@@ -1811,7 +1811,7 @@ def check_two_pass_splitk(dev, kind, sk):
         ops.force_plan(0)
 
 
-STREAM_K = 2000000     # GemmPlan.splitk == kStreamK
+STREAM_K = 2000000     # splitk == STREAM_K: stream-K (same paragraph of include/transfuser_hip.h)
 STREAM_K_KINDS_EMU = [2, 6]
 STREAM_K_KINDS_GPU = [1, 2, 3, 4, 5, 6, 7, 8]
 

@@ -53,6 +53,11 @@ def test_engine_ksplit_conv_wgrad(case):
     dc.check_engine_ksplit_conv(DEV, *case)
 
 
+@pytest.mark.parametrize("site", dc.QUERY_SITES)
+def test_scratch_query_agrees_with_launch(site):
+    dc.check_scratch_query_agrees(DEV, site)
+
+
 @pytest.mark.parametrize("rows,C", dc.LN_CASES)
 def test_layernorm_dw(rows, C):
     dc.check_layernorm_dw(DEV, rows, C)

@@ -44,6 +44,11 @@ def test_engine_conv_case_list_covers_the_new_case():
     assert (2, 12, 20, 40, 72, 3, 2, 1) in cases and any(c[7] == 1 for c in cases)
 
 
+@pytest.mark.parametrize("site", dc.QUERY_SITES)
+def test_scratch_query_agrees_with_launch(site):
+    dc.check_scratch_query_agrees(DEV, site)
+
+
 # 3. the other sites
 @pytest.mark.parametrize("rows,C", dc.LN_CASES)
 def test_layernorm_dw(rows, C):

@@ -10,7 +10,7 @@ ops.set_precision(prec)
 ops.plans_load(os.path.join(ROOT, "transfuser_amd", "plans", "mi355x.txt"))
 dev = "cuda"
 REP = 10
-SK = 2000000
+SK = 2000000      # the stream-K code of the splitk encoding (include/transfuser_hip.h, at tf_force_plan / tf_force_dma)
 
 
 def graph_time(fn, rep=REP):

@@ -90,8 +90,21 @@ int device_cus() {
     return n;
 #endif
 }
-static GemmPlan g_forced{0, 0, 0, 0, 0};
+static GemmPlan g_forced{0, 0, 0};
 bool forced_plan(GemmPlan* out) { if (g_forced.bm == 0) return false; *out = g_forced; return true; }
+
+// The integer "splitk" of the plan file (tf_plans_load / tf_plans_save) and of the test pins (tf_force_plan / tf_force_dma), documented in
+// include/transfuser_hip.h: 1 = no k-split, 2..999999 = that many atomic k-slices, 1000000 + S = two-pass split with S slices, 2000000 = stream-K.
+// These two functions are the only place that knows it.
+constexpr int kTwoPassCode = 1000000, kStreamKCode = 2000000;
+static GemmPlan plan_decode(int bm, int bn, int bk, int splitk, int kind) {
+    if (splitk == kStreamKCode) return {bm, bn, bk, kind, KSplit::StreamK, 1};
+    if (splitk >= kTwoPassCode) return {bm, bn, bk, kind, KSplit::TwoPass, splitk - kTwoPassCode};
+    return atomic_plan(bm, bn, bk, kind, splitk);
+}
+static int plan_encode(const GemmPlan& p) {
+    return p.split == KSplit::StreamK ? kStreamKCode : p.split == KSplit::TwoPass ? kTwoPassCode + p.slices : p.slices;
+}
 }  // namespace tf
 
 static bool plan_tile_ok(int bm, int bn, int bk, int sk, int kind) {
@@ -105,13 +118,13 @@ extern "C" int tf_gemm_epi16(int on) {
 extern "C" int tf_force_dma(int kind, int splitk) {
     if (kind < 1 || kind > tf::kDmaKinds || splitk < 1) { tf::set_error("tf_force_dma: unknown LDS-DMA configuration %d", kind); return -1; }
     const tf::DmaKindInfo ki = tf::dma_kind_info(kind);
-    tf::g_forced = tf::GemmPlan{ki.bm, ki.bn, ki.bk, splitk, kind};
+    tf::g_forced = tf::plan_decode(ki.bm, ki.bn, ki.bk, splitk, kind);
     return 0;
 }
 extern "C" int tf_force_plan(int bm, int bn, int bk, int splitk) {
     const bool ok = bm == 0 || (((bm == 128 && (bn == 32 || bn == 64 || bn == 96 || bn == 128)) || (bm == 64 && (bn == 64 || bn == 128))) && (bk == 16 || bk == 32) && splitk >= 1);
     if (!ok) { tf::set_error("tf_force_plan: unsupported tiling %dx%dx%d", bm, bn, bk); return -1; }
-    tf::g_forced = tf::GemmPlan{bm, bn, bk, splitk, 0};
+    tf::g_forced = tf::plan_decode(bm, bn, bk, splitk, 0);
     return 0;
 }
 namespace tf {
@@ -136,7 +149,7 @@ extern "C" int tf_plans_save(const char* path) {
     fprintf(f, "# transfuser_hip GEMM plans: site;M;N;K;batch;acc;bm;bn;bk;splitk;kind   (kind 0 = register-staged kernel, >= 1 = LDS-DMA configuration; splitk >= 1000000 = deterministic two-pass split-K with splitk - 1000000 slices)\n");
     for (auto& kv : tf::g_plans)
         fprintf(f, "%s;%d;%d;%d;%d;%d;%d;%d;%d;%d;%d\n", std::get<0>(kv.first).c_str(), std::get<1>(kv.first), std::get<2>(kv.first), std::get<3>(kv.first),
-                std::get<4>(kv.first), std::get<5>(kv.first), kv.second.bm, kv.second.bn, kv.second.bk, kv.second.splitk, kv.second.kind);
+                std::get<4>(kv.first), std::get<5>(kv.first), kv.second.bm, kv.second.bn, kv.second.bk, tf::plan_encode(kv.second), kv.second.kind);
     fclose(f);
     return 0;
 }
@@ -154,7 +167,7 @@ extern "C" int tf_plans_load(const char* path) {
         memcpy(site, line, semi - line); site[semi - line] = 0;
         if (sscanf(semi + 1, "%d;%d;%d;%d;%d;%d;%d;%d;%d;%d", &M, &N, &K, &b, &acc, &bm, &bn, &bk, &sk, &kind) < 9) continue;   // 10th field optional (r01 files)
         if (!plan_tile_ok(bm, bn, bk, sk, kind)) continue;
-        tf::plan_store(site, M, N, K, b, acc, tf::GemmPlan{bm, bn, bk, sk, kind});
+        tf::plan_store(site, M, N, K, b, acc, tf::plan_decode(bm, bn, bk, sk, kind));
         ++n;
     }
     fclose(f);

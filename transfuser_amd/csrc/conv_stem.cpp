@@ -38,6 +38,15 @@ extern "C" int tf_stem_conv_fwd_f32(const tf_conv_geom* g, const float* s0, int 
     return launch_gemm<Im2colNchwOp, true, PlainOp, true>(A, Bw, ep, M, g->Cout, K, 1, false, stream, "tf_stem_conv_fwd_f32");
 }
 
+// the epilogue of the implicit-GEMM weight gradient, as the launch uses it and as the scratch query describes it to resolve_plan()
+static GemmEpi stem_wgrad_epi(const tf_conv_geom* g, float* dw, int accumulate, float* ws, long ws_floats) {
+    GemmEpi ep;
+    ep.C = dw; ep.ldc = g->ksize * g->ksize * g->Cin; ep.ldcj = 1; ep.sc_outer = 0; ep.sc_inner = 0; ep.inner = 1; ep.bias = nullptr; ep.sbias = 0; ep.res = nullptr; ep.ldres = 0;
+    ep.alpha = 1.f; ep.relu = 0; ep.mode = accumulate ? 1 : 0;
+    ep.sk_ws = (ws && aligned16(ws)) ? ws : nullptr; ep.sk_ws_floats = ep.sk_ws ? ws_floats : 0;
+    return ep;
+}
+
 // the implicit-GEMM weight gradient; (ws, ws_floats): optional caller scratch for the ordered slab k-split of the deterministic mode (launch_gemm)
 static int stem_engine_wgrad(const tf_conv_geom* g, const float* dy, const float* s0, int C0, const float* s1, int C1, int normalize, float* dw, int accumulate,
                              float* ws, long ws_floats, void* stream) {
@@ -48,10 +57,7 @@ static int stem_engine_wgrad(const tf_conv_geom* g, const float* dy, const float
     A.p = dy; A.ld = g->Cout; A.rows = M; A.cols = g->Cout; A.s_outer = 0; A.s_inner = 0; A.inner = 1;
     A.vec = (aligned16(dy) && g->Cout % 4 == 0) ? 1 : 0;
     Im2colNchwOp Bx = make_stem(g, s0, C0, s1, C1, normalize);
-    GemmEpi ep;
-    ep.C = dw; ep.ldc = K; ep.ldcj = 1; ep.sc_outer = 0; ep.sc_inner = 0; ep.inner = 1; ep.bias = nullptr; ep.sbias = 0; ep.res = nullptr; ep.ldres = 0;
-    ep.alpha = 1.f; ep.relu = 0; ep.mode = accumulate ? 1 : 0;
-    ep.sk_ws = (ws && aligned16(ws)) ? ws : nullptr; ep.sk_ws_floats = ep.sk_ws ? ws_floats : 0;
+    const GemmEpi ep = stem_wgrad_epi(g, dw, accumulate, ws, ws_floats);
     return launch_gemm<PlainOp, false, Im2colNchwOp, false>(A, Bx, ep, g->Cout, K, M, 1, true, stream, "tf_stem_conv_wgrad_f32");
 }
 
@@ -66,7 +72,8 @@ extern "C" int tf_stem_conv_wgrad_f32(const tf_conv_geom* g, const float* dy, co
 extern "C" long tf_stem_conv_wgrad_ws_floats(const tf_conv_geom* g, int C0, int C1) {
     if (!g) return 0;
     if (stem_direct_ok(g, C0, C1)) return stem_direct_wgrad_ws_floats(g);
-    return deterministic() ? slab_ws_floats("tf_stem_conv_wgrad_f32", g->Cout, g->ksize * g->ksize * g->Cin, g->B * g->Ho * g->Wo) : 0;
+    return plan_scratch_floats(plan_call("tf_stem_conv_wgrad_f32", g->Cout, g->ksize * g->ksize * g->Cin, g->B * g->Ho * g->Wo, 1, true, true, false,
+                                         stem_wgrad_epi(g, nullptr, 1, nullptr, 0)));
 }
 extern "C" int tf_stem_conv_wgrad_ws_f32(const tf_conv_geom* g, const float* dy, const float* s0, int C0, const float* s1, int C1, int normalize, float* dw,
                                          int accumulate, float* ws, long ws_floats, void* stream) {

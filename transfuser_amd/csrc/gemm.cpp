@@ -1,6 +1,7 @@
 // tf_gemm_f32: batched strided fp32 GEMM on the MFMA engine (plain operands).
 #include "tf_gemm_engine.h"
 #include <stdlib.h>
+#include <utility>
 #include "../../include/transfuser_hip.h"
 
 using namespace tf;
@@ -39,33 +40,56 @@ static PlainOp make_plain(const float* p, long ld, int rows, int cols, long so, 
     return o;
 }
 
-// Scratch floats tf_gemm_f32 can use for this call's deterministic two-pass split-K (tf_gemm_desc.splitk_ws): 0 when the cached plan of the
-// call's site / shape is not a two-pass plan (so the caller need not allocate anything), the S-slice size when it is, and the 4-slice
-// maximum while the autotuner is on or a test pins a two-pass plan (the candidates need the scratch to be tried at all).
+// [tn] weight gradient with few output rows (m = out features <= 32 << n): compute C^T so the short side becomes the 32-wide column tile
+// instead of a 128-row tile (4x less MFMA padding); stores go through the column stride.  Not for a deterministic accumulation: the ordered slab
+// k-split needs a row-major output, so that mode keeps the unswapped orientation.
+static bool tn_swapped(const tf_gemm_desc* d) {
+    return d->a_trans && d->b_trans && d->m <= 32 && d->n >= 2 * d->m && !d->bias && !d->res && !d->relu && !(deterministic() && d->accumulate);
+}
+
+// The engine call of a descriptor - operands, epilogue, orientation and site name - as tf_gemm_f32 launches it and as tf_gemm_splitk_ws_floats
+// asks resolve_plan() about it.
+struct EngineCall { PlainOp A, B; GemmEpi ep; int M, N; bool swapped; const char* site; };
+static EngineCall engine_call(const tf_gemm_desc* d) {
+    EngineCall e;
+    const int inner = d->inner > 0 ? d->inner : 1;
+    GemmEpi& ep = e.ep;
+    ep.C = d->c; ep.ldc = d->ldc; ep.ldcj = 1; ep.sc_outer = d->sc_outer; ep.sc_inner = d->sc_inner; ep.inner = inner;
+    ep.bias = d->bias; ep.sbias = 0; ep.res = d->res; ep.ldres = d->ldres; ep.alpha = d->alpha; ep.relu = d->relu;
+    ep.mode = d->accumulate ? 1 : 0;
+    ep.mask = d->mask; ep.ldmask = d->ldmask;
+    ep.sk_ws = d->splitk_ws; ep.sk_ws_floats = d->splitk_ws ? d->splitk_ws_floats : 0;
+    ep.sk_flags = d->splitk_ws ? d->sk_flags : nullptr;
+    if (d->colstat) { ep.stat = d->colstat; ep.stat_ld = d->n; ep.stat_nparts = d->colstat_nparts; }
+    if (d->drop_seed) { ep.drop_seed = d->drop_seed; ep.drop_site = d->drop_site; ep.drop_thresh = (uint32_t)((double)d->drop_p * 4294967296.0); ep.drop_scale = 1.f / (1.f - d->drop_p); }
+    // A: KC when stored [m][k] (rows = i), IC when stored [k][m] (rows = k)
+    e.A = d->a_trans ? make_plain(d->a, d->lda, d->k, d->m, d->sa_outer, d->sa_inner, inner, d->batch)
+                     : make_plain(d->a, d->lda, d->m, d->k, d->sa_outer, d->sa_inner, inner, d->batch);
+    // B: KC when stored [n][k] (rows = j), IC when stored [k][n] (rows = k)
+    e.B = d->b_trans ? make_plain(d->b, d->ldb, d->k, d->n, d->sb_outer, d->sb_inner, inner, d->batch)
+                     : make_plain(d->b, d->ldb, d->n, d->k, d->sb_outer, d->sb_inner, inner, d->batch);
+    e.M = d->m; e.N = d->n;
+    e.swapped = tn_swapped(d);
+    if (e.swapped) { std::swap(e.A, e.B); std::swap(e.M, e.N); ep.ldc = 1; ep.ldcj = d->ldc; }
+    e.site = e.swapped ? "tf_gemm_f32[tn,swapped]"
+                       : !d->a_trans ? (d->b_trans ? "tf_gemm_f32[nn]" : "tf_gemm_f32[nt]") : (d->b_trans ? "tf_gemm_f32[tn]" : "tf_gemm_f32[tt]");
+    return e;
+}
+
+// Scratch floats tf_gemm_f32 can use for this call (tf_gemm_desc.splitk_ws): what the plan resolve_plan() gives the call uses when the scratch
+// is there - the slices of a two-pass or (tf_set_deterministic) ordered slab k-split, the partial tiles of a stream-K plan, the autotuner's
+// four-slice maximum while it still has to try such plans - or the block partials of the skinny weight gradient under the flag; 0 = nothing to bring.
 extern "C" long tf_gemm_splitk_ws_floats(const tf_gemm_desc* d) {
     if (!d || d->batch != 1 || d->m <= 0 || d->n <= 0 || d->k <= 0) return 0;
-    const bool det_acc = deterministic() && d->accumulate && !d->bias && !d->res && !d->relu;      // tf_set_deterministic: the fixed-order forms of the accumulating calls
-    if (det_acc && skinny_route(d)) return skinny_wgrad_ws_floats(d->k, d->m, d->n);
-    const long slice = (long)d->m * twopass_ldws(d->n);
-    GemmPlan p;
-    const long sk_floats = (long)kStreamKMaxBlocks / 4 * 128 * 128;       // stream-K: <= 512 resident workgroups x one 128 x 128 partial tile (larger launches use smaller tiles)
-    const char* site = !d->a_trans ? (d->b_trans ? "tf_gemm_f32[nn]" : "tf_gemm_f32[nt]") : (d->b_trans ? "tf_gemm_f32[tn]" : "tf_gemm_f32[tt]");
-    int M = d->m, N = d->n;
-    if (det_acc && d->a_trans && d->b_trans) { const long need = slab_ws_floats(site, M, N, d->k); if (need > 0) return need; }      // ordered slab k-split (the swapped orientation is not taken in this mode)
-    if (forced_plan(&p)) return p.splitk == kStreamK ? sk_floats : p.splitk >= kTwoPass ? 4 * slice : 0;
-    if (det_acc) {}
-    else if (d->a_trans && d->b_trans && d->m <= 32 && d->n >= 2 * d->m && !d->bias && !d->res && !d->relu) return 0;       // swapped (column-strided) output: no two-pass
-    const bool sk_ok = d->accumulate && !d->bias && !d->res && !d->relu;
-    const int acc = (d->accumulate ? (sk_ok ? 2 : 1) : 0) + 4 * (gemm_precision() == 3 ? 1 : gemm_precision());
-    if (plan_lookup(site, M, N, d->k, 1, acc, &p)) return p.splitk == kStreamK ? sk_floats : p.splitk >= kTwoPass ? (long)(p.splitk - kTwoPass) * slice : 0;
-    return autotune_enabled() ? (4 * slice > sk_floats ? 4 * slice : sk_floats) : 0;
+    if (deterministic() && d->accumulate && !d->bias && !d->res && !d->relu && skinny_route(d)) return skinny_wgrad_ws_floats(d->k, d->m, d->n);
+    const EngineCall e = engine_call(d);
+    return plan_scratch_floats(plan_call(e.site, e.M, e.N, d->k, d->batch, d->accumulate != 0, d->a_trans && d->b_trans, dma_eligible(e.A, e.B), e.ep));
 }
 
 extern "C" int tf_gemm_f32(const tf_gemm_desc* d, void* stream) {
     TF_REQUIRE(d && d->a && d->b && d->c, "tf_gemm_f32: null operand");
     TF_REQUIRE(d->m >= 0 && d->n >= 0 && d->k >= 0 && d->batch >= 1, "tf_gemm_f32: bad sizes m=%d n=%d k=%d batch=%d", d->m, d->n,
                d->k, d->batch);
-    const int inner = d->inner > 0 ? d->inner : 1;
     // per-sample matmuls (SE excitation, join MLP): rows = batch <= 16 -> streaming kernels instead of a 128-row MFMA tile
     if (d->batch == 1 && d->alpha == 1.0f && d->m > 0 && d->n > 0 && d->k > 0 && !d->mask && !d->colstat && !d->drop_seed) {
         if (!d->a_trans && !d->b_trans && d->m <= 16 && !d->accumulate)
@@ -78,45 +102,20 @@ extern "C" int tf_gemm_f32(const tf_gemm_desc* d, void* stream) {
         if (skinny_route(d))
             return skinny_wgrad(d->a, d->lda, d->b, d->ldb, d->c, d->ldc, d->k, d->m, d->n, d->splitk_ws, d->splitk_ws ? d->splitk_ws_floats : 0, stream);
     }
-    GemmEpi ep;
-    ep.C = d->c; ep.ldc = d->ldc; ep.ldcj = 1; ep.sc_outer = d->sc_outer; ep.sc_inner = d->sc_inner; ep.inner = inner;
-    ep.bias = d->bias; ep.sbias = 0; ep.res = d->res; ep.ldres = d->ldres; ep.alpha = d->alpha; ep.relu = d->relu;
-    ep.mode = d->accumulate ? 1 : 0;
-    ep.mask = d->mask; ep.ldmask = d->ldmask;
-    ep.sk_ws = d->splitk_ws; ep.sk_ws_floats = d->splitk_ws ? d->splitk_ws_floats : 0;
-    ep.sk_flags = d->splitk_ws ? d->sk_flags : nullptr;
     if (d->colstat) {
         TF_REQUIRE(d->colstat_nparts && d->batch == 1 && !d->accumulate && !d->res && !d->relu && !d->mask && !d->a_trans,
                    "tf_gemm_f32: colstat needs a plain store (batch 1, no residual / ReLU / mask / accumulate), row-major A and colstat_nparts");
-        ep.stat = d->colstat; ep.stat_ld = d->n; ep.stat_nparts = d->colstat_nparts;
         *d->colstat_nparts = 0;
     }
     TF_REQUIRE(!d->mask || (d->batch == 1 && !d->accumulate), "tf_gemm_f32: mask needs batch == 1 and a plain store");
-    if (d->drop_seed) {
-        TF_REQUIRE(d->batch == 1 && !d->accumulate && !d->a_trans && d->ldc == d->n && d->drop_p >= 0.f && d->drop_p < 1.f && !d->colstat && (long)d->m * d->n < 4294967296L,
-                   "tf_gemm_f32: drop_seed needs batch 1, a plain store into a contiguous (m, n) output, row-major A and 0 <= drop_p < 1");
-        ep.drop_seed = d->drop_seed; ep.drop_site = d->drop_site; ep.drop_thresh = (uint32_t)((double)d->drop_p * 4294967296.0); ep.drop_scale = 1.f / (1.f - d->drop_p);
-    }
-    // A: KC when stored [m][k] (rows = i), IC when stored [k][m] (rows = k)
-    PlainOp A = d->a_trans ? make_plain(d->a, d->lda, d->k, d->m, d->sa_outer, d->sa_inner, inner, d->batch)
-                           : make_plain(d->a, d->lda, d->m, d->k, d->sa_outer, d->sa_inner, inner, d->batch);
-    // B: KC when stored [n][k] (rows = j), IC when stored [k][n] (rows = k)
-    PlainOp B = d->b_trans ? make_plain(d->b, d->ldb, d->k, d->n, d->sb_outer, d->sb_inner, inner, d->batch)
-                           : make_plain(d->b, d->ldb, d->n, d->k, d->sb_outer, d->sb_inner, inner, d->batch);
+    TF_REQUIRE(!d->drop_seed || (d->batch == 1 && !d->accumulate && !d->a_trans && d->ldc == d->n && d->drop_p >= 0.f && d->drop_p < 1.f && !d->colstat && (long)d->m * d->n < 4294967296L),
+               "tf_gemm_f32: drop_seed needs batch 1, a plain store into a contiguous (m, n) output, row-major A and 0 <= drop_p < 1");
+    const EngineCall e = engine_call(d);
     const bool sk = d->accumulate != 0;
-    if (!d->a_trans && !d->b_trans) return gemm_plain_nt(A, B, ep, d->m, d->n, d->k, d->batch, sk, stream, "tf_gemm_f32[nt]");
-    if (!d->a_trans && d->b_trans) return gemm_plain_nn(A, B, ep, d->m, d->n, d->k, d->batch, sk, stream, "tf_gemm_f32[nn]");
-    if (d->a_trans && d->b_trans) {
-        // weight gradient with few output rows (m = out features <= 32 << n): compute C^T so the short side becomes the
-        // 32-wide column tile instead of a 128-row tile (4x less MFMA padding); stores go through the column stride.
-        // (not in the deterministic mode: the ordered slab k-split needs a row-major output, so that mode keeps the unswapped orientation)
-        if (d->m <= 32 && d->n >= 2 * d->m && !d->bias && !d->res && !d->relu && !(deterministic() && d->accumulate)) {
-            ep.ldc = 1; ep.ldcj = d->ldc;
-            return gemm_plain_tn(B, A, ep, d->n, d->m, d->k, d->batch, sk, stream, "tf_gemm_f32[tn,swapped]");
-        }
-        return gemm_plain_tn(A, B, ep, d->m, d->n, d->k, d->batch, sk, stream, "tf_gemm_f32[tn]");
-    }
-    return gemm_plain_tt(A, B, ep, d->m, d->n, d->k, d->batch, sk, stream, "tf_gemm_f32[tt]");
+    if (!d->a_trans && !d->b_trans) return gemm_plain_nt(e.A, e.B, e.ep, e.M, e.N, d->k, d->batch, sk, stream, e.site);
+    if (!d->a_trans && d->b_trans) return gemm_plain_nn(e.A, e.B, e.ep, e.M, e.N, d->k, d->batch, sk, stream, e.site);
+    if (d->a_trans && d->b_trans) return gemm_plain_tn(e.A, e.B, e.ep, e.M, e.N, d->k, d->batch, sk, stream, e.site);
+    return gemm_plain_tt(e.A, e.B, e.ep, e.M, e.N, d->k, d->batch, sk, stream, e.site);
 }
 
 // ---- packed 16-bit operands: C (op)= alpha * A16 . B16^T (+ bias) (+ res) (relu) (mask), fp32 accumulate / output.
@@ -174,7 +173,7 @@ int gemm16_impl(const void* a16, const void* b16, float* c, int m, int n, int k,
             if (s >= 2) { splitk = (int)s; ep.mode = 2; }
         }
     }
-    launch_dma_plan<true, true>(kind, A, B, ep, m, n, k / 2, 1, splitk, stream);
+    launch_dma_plan<true, true>(kind, A, B, ep, m, n, k / 2, 1, splitk > 1 ? KSplit::Atomic : KSplit::None, splitk, stream);
     return launch_status("tf_gemm16_nt_f32");
 }
 }  // namespace tf

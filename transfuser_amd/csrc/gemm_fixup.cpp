@@ -1,4 +1,4 @@
-// Second pass of the deterministic two-pass split-K (tf_gemm_dma.h / tf_gemm_engine.h: kTwoPass): the k-slices of a GEMM whose output has too
+// Second pass of the deterministic two-pass split-K (tf_gemm_dma.h / tf_gemm_engine.h: KSplit::TwoPass, KSplit::Slab): the k-slices of a GEMM whose output has too
 // few tiles for the 256 CUs stored raw partial tiles ws[s][M][ldws]; here they are summed IN SLICE ORDER (bitwise reproducible, unlike the
 // atomic split-K of the weight gradients) and the GEMM epilogue proper is applied: alpha, bias, residual, ReLU, mask, store / +=.
 // HBM-bound: (S + res + mask) reads + one write of the M x N output, float4 where the output allows it.

@@ -13,7 +13,7 @@ thread_local Held g_held[2];
 thread_local long g_pairs = 0, g_singles = 0;
 
 PairSide side_of(const Held& h) {
-    const CfgGeom cg = cfg_geom(h.ep, h.M, h.N, h.K, h.p.splitk, 64, 64, h.p.bk, 2);
+    const CfgGeom cg = cfg_geom(h.ep, h.M, h.N, h.K, h.p.slices, 64, 64, h.p.bk, 2);
     PairSide s;
     s.la = h.la; s.lb = h.lb; s.ep = cg.epg; s.M = h.M; s.N = h.N; s.K = h.K;
     s.tiles_m = cg.tiles_m; s.tiles_n = cg.tiles_n; s.kchunk = cg.kchunk; s.gx = cg.tiles_m * cg.tiles_n; s.gy = cg.nsplit;
@@ -23,8 +23,8 @@ PairSide side_of(const Held& h) {
 // a held call is always a 64 x 64 register-staged plan (tf_gemm_engine.h:launch_gemm): the same launch launch_plan would have issued
 template <bool A_KC, bool B_KC>
 void launch_single(const Held& h, void* stream) {
-    if (h.p.bk == 32) launch_cfg<64, 64, 2, 32, PlainOp, A_KC, PlainOp, B_KC>(h.la, h.lb, h.ep, h.M, h.N, h.K, 1, h.p.splitk, stream);
-    else launch_cfg<64, 64, 2, 16, PlainOp, A_KC, PlainOp, B_KC>(h.la, h.lb, h.ep, h.M, h.N, h.K, 1, h.p.splitk, stream);
+    if (h.p.bk == 32) launch_cfg<64, 64, 2, 32, PlainOp, A_KC, PlainOp, B_KC>(h.la, h.lb, h.ep, h.M, h.N, h.K, 1, h.p.split, h.p.slices, stream);
+    else launch_cfg<64, 64, 2, 16, PlainOp, A_KC, PlainOp, B_KC>(h.la, h.lb, h.ep, h.M, h.N, h.K, 1, h.p.split, h.p.slices, stream);
 }
 
 void launch_alone(const Held& h, void* stream) {

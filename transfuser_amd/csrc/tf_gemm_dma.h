@@ -445,52 +445,34 @@ inline bool dma_eligible_impl(const PlainOp& a, const PlainOp& b) {
     return ok(a) && ok(b);
 }
 
+// split / slices: the plan's k-partition as resolve_plan() left it (eligibility is checked there) - StreamK: slices = workgroups of the launch;
+// TwoPass and Slab: the k-slices go through the caller's scratch and the fix-up pass; Atomic: the caller's epilogue has mode 2
 template <int TM, int TN, int WAVES_M, int WAVES_N, int BK, int STAGES, bool A_KC, bool B_KC, int OCC>
-inline void launch_dma_cfg(const PlainOp& la, const PlainOp& lb, const GemmEpi& ep, int M, int N, int K, int batch, int splitk, void* stream) {
+inline void launch_dma_cfg(const PlainOp& la, const PlainOp& lb, const GemmEpi& ep, int M, int N, int K, int batch, KSplit split, int slices, void* stream) {
     typedef DmaCfg<TM, TN, WAVES_M, WAVES_N, BK, STAGES, A_KC, B_KC> C;
     const int tiles_m = cdiv(M, C::BM), tiles_n = cdiv(N, C::BN);
-    if (splitk == kStreamK) {                       // eligibility was checked by launch_gemm (streamk_blocks > 0)
-        const int P = streamk_blocks(ep, M, N, K, batch, C::BM, C::BN, BK, C::NW, OCC, C::LDS_BYTES);
+    if (split == KSplit::StreamK) {
         streamk_count(1);
         GemmEpi eps = ep;
         eps.prec = ep.packed16 ? 0 : gemm_precision();
-        {
-            long panel = (long)C::BM * K * 4;
-            int g = (int)((2L << 20) / (panel > 0 ? panel : 1));
-            if (g > 8) g = 8;
-            if (g > tiles_m) g = tiles_m;
-            eps.group_m = (g >= 2 && tiles_n >= 4) ? g : 1;
-        }
+        eps.group_m = raster_group_m(C::BM, K, tiles_m, tiles_n);
         if (eps.stat_nparts) *eps.stat_nparts = eps.stat ? cdiv(M, 32 * TM) : 0;
         if (eps.prec == 2 && !ep.packed16)
-            TF_LAUNCH((gemm_dma_sk_kernel<TM, TN, WAVES_M, WAVES_N, BK, STAGES, A_KC, B_KC, OCC, true>), dim3(P), dim3(C::NT), stream, la, lb, eps, M, N, K, tiles_m, tiles_n);
+            TF_LAUNCH((gemm_dma_sk_kernel<TM, TN, WAVES_M, WAVES_N, BK, STAGES, A_KC, B_KC, OCC, true>), dim3(slices), dim3(C::NT), stream, la, lb, eps, M, N, K, tiles_m, tiles_n);
         else
-            TF_LAUNCH((gemm_dma_sk_kernel<TM, TN, WAVES_M, WAVES_N, BK, STAGES, A_KC, B_KC, OCC, false>), dim3(P), dim3(C::NT), stream, la, lb, eps, M, N, K, tiles_m, tiles_n);
+            TF_LAUNCH((gemm_dma_sk_kernel<TM, TN, WAVES_M, WAVES_N, BK, STAGES, A_KC, B_KC, OCC, false>), dim3(slices), dim3(C::NT), stream, la, lb, eps, M, N, K, tiles_m, tiles_n);
         return;
     }
-    const bool twopass = splitk >= kTwoPass;       // eligibility was checked by launch_gemm (twopass_ok)
-    if (twopass) splitk -= kTwoPass;
-    int kchunk = cdiv(cdiv(K, splitk), BK) * BK;
+    const bool twopass = split == KSplit::TwoPass || split == KSplit::Slab;
+    int kchunk = cdiv(cdiv(K, split == KSplit::None ? 1 : slices), BK) * BK;
     if (kchunk < BK) kchunk = BK;
     const int nsplit = cdiv(K, kchunk);
     dim3 grid(tiles_m * tiles_n, nsplit > 0 ? nsplit : 1, batch);
-    GemmEpi epg = ep;
+    GemmEpi epg = twopass ? slice_epilogue(ep, M, N) : ep;
     epg.prec = ep.packed16 ? 0 : gemm_precision();
-    const int ldws = twopass_ldws(N);
-    if (twopass) {      // slices store raw partial sums [M][ldws] into the caller's scratch; the epilogue proper runs in the fix-up pass
-        epg.C = ep.sk_ws; epg.ldc = ldws; epg.ldcj = 1; epg.sc_outer = epg.sc_inner = 0; epg.inner = 1; epg.bias = nullptr; epg.res = nullptr;
-        epg.mask = nullptr; epg.alpha = 1.f; epg.relu = 0; epg.mode = 0; epg.sk_stride = (long)M * ldws;
-        epg.drop_seed = nullptr;
-    }
-    {
-        long panel = (long)C::BM * (kchunk < K ? kchunk : K) * 4;
-        int g = (int)((2L << 20) / (panel > 0 ? panel : 1));
-        if (g > 8) g = 8;
-        if (g > tiles_m) g = tiles_m;
-        epg.group_m = (g >= 2 && tiles_n >= 4) ? g : 1;
-    }
+    epg.group_m = raster_group_m(C::BM, kchunk < K ? kchunk : K, tiles_m, tiles_n);
     if (epg.mode == 2) float_atomic_count(1);
-    if (twopass || nsplit > 1) epg.stat = nullptr;          // (launch_gemm never sends a statistics request down a k-split plan)
+    if (nsplit > 1) epg.stat = nullptr;          // (resolve_plan never sends a statistics request down a k-split plan)
     if (epg.stat_nparts) *epg.stat_nparts = epg.stat ? cdiv(M, 32 * TM) : 0;
     if (epg.prec == 2 && !ep.packed16)
         TF_LAUNCH((gemm_dma_kernel<TM, TN, WAVES_M, WAVES_N, BK, STAGES, A_KC, B_KC, OCC, true>), grid, dim3(C::NT), stream, la, lb, epg, M, N, K,
@@ -498,7 +480,7 @@ inline void launch_dma_cfg(const PlainOp& la, const PlainOp& lb, const GemmEpi& 
     else
         TF_LAUNCH((gemm_dma_kernel<TM, TN, WAVES_M, WAVES_N, BK, STAGES, A_KC, B_KC, OCC, false>), grid, dim3(C::NT), stream, la, lb, epg, M, N, K,
                   tiles_m, tiles_n, kchunk);
-    if (twopass) launch_splitk_fixup(ep.sk_ws, nsplit, (long)M * ldws, ldws, ep, M, N, stream);
+    if (twopass) launch_splitk_fixup(ep.sk_ws, nsplit, epg.sk_stride, epg.ldc, ep, M, N, stream);
 }
 
 }  // namespace tf

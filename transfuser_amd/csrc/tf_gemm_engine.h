@@ -844,7 +844,14 @@ __global__ void __launch_bounds__(256, 4) gemm_pair_kernel(PairSide s1, PairSide
 // ---------------------------------------------------------------- host dispatch
 // kind 0: gemm_kernel (register-staged, any loader).  kind >= 1: LDS-DMA kernel configuration of tf_gemm_dma.h (plain vector operands
 // only; bm/bn/bk then mirror that configuration's tile for the plan file's readers).
-struct GemmPlan { int bm, bn, bk, splitk; int kind = 0; };
+// How a plan partitions K.  Atomic: `slices` k-slices that add into C with float atomics (epilogue mode 2).  TwoPass: `slices` k-slices store raw
+// partial tiles into the caller's scratch, gemm_fixup.cpp adds them in slice order (LDS-DMA kinds only).  StreamK: persistent workgroups over the
+// (tile, k-tile) space, `slices` = workgroups of the launch (LDS-DMA kinds only).  Slab: the ordered slab split that replaces an atomic split in
+// the deterministic mode - never stored or pinned, only resolve_plan() produces it.  None: slices == 1.
+// The integer form of the plan file and the test pins exists in api.cpp only (plan_decode / plan_encode).
+enum class KSplit { None, Atomic, TwoPass, StreamK, Slab };
+struct GemmPlan { int bm, bn, bk; int kind = 0; KSplit split = KSplit::None; int slices = 1; };
+inline GemmPlan atomic_plan(int bm, int bn, int bk, int kind, int slices) { return {bm, bn, bk, kind, slices > 1 ? KSplit::Atomic : KSplit::None, slices > 1 ? slices : 1}; }
 
 // LDS-DMA configurations (tf_gemm_dma.h); the launchers live in gemm_dma_{nt,nn,tn,tt}.cpp (one translation unit per operand layout)
 constexpr int kDmaKinds = 8;
@@ -855,53 +862,29 @@ inline DmaKindInfo dma_kind_info(int kind) {
     return t[(kind >= 1 && kind <= kDmaKinds) ? kind : 0];
 }
 template <bool A_KC, bool B_KC>
-void launch_dma_plan(int kind, const PlainOp& la, const PlainOp& lb, const GemmEpi& ep, int M, int N, int K, int batch, int splitk, void* stream);
+void launch_dma_plan(int kind, const PlainOp& la, const PlainOp& lb, const GemmEpi& ep, int M, int N, int K, int batch, KSplit split, int slices, void* stream);
 bool dma_eligible(const PlainOp& a, const PlainOp& b);
 
 // two-pass split-K (gemm_fixup.cpp): C (op)= epilogue(sum_s ws[s]) with the slices summed in order; ws slices are [M][ldws] row-major
 void launch_splitk_fixup(const float* ws, int nsplit, long sk_stride, int ldws, const GemmEpi& ep, int M, int N, void* stream);
-constexpr int kStreamK = 2000000;  // GemmPlan.splitk == kStreamK: stream-K (persistent workgroups over the (tile, k-tile) space; LDS-DMA kinds only, tf_gemm_dma.h)
 constexpr int kStreamKMaxBlocks = 2048;
 int device_cus();                  // api.cpp: compute units of the current device (cached)
 long streamk_count(int add);       // api.cpp: stream-K launches so far (tests assert that a pinned stream-K plan really ran as one)
-// workgroups of a stream-K launch of this configuration, 0 = not eligible: single-batch, non-atomic epilogue, caller scratch + flags, at least one
-// whole tile of work per workgroup (so a tile is cut at most once) and a tile count that does NOT already divide evenly over the resident slots
-inline int streamk_blocks(const GemmEpi& ep, int M, int N, int K, int batch, int bm, int bn, int bk, int nw, int occ, int lds_bytes) {
-    if (!ep.sk_ws || !ep.sk_flags || batch != 1 || ep.mode == 2 || K < 8 * bk) return 0;
-    int per_cu = occ * 4 / nw;                                 // __launch_bounds__(64 nw, occ): occ waves per SIMD
-    const int by_lds = (160 * 1024) / (lds_bytes > 0 ? lds_bytes : 1);
-    if (per_cu > by_lds) per_cu = by_lds;
-    if (per_cu < 1) per_cu = 1;
-    const long nt = (long)cdiv(M, bm) * cdiv(N, bn);
-    long P = (long)device_cus() * per_cu;
-    if (P > kStreamKMaxBlocks) P = kStreamKMaxBlocks;
-    if (P > nt) P = nt;
-    P &= ~7L;                                                  // XCD-contiguous positions
-    if (P < 8 || nt % P == 0) return 0;                        // already balanced: the data-parallel launch is the same thing without the bookkeeping
-    if (P * (long)bm * bn > ep.sk_ws_floats) return 0;
-    return (int)P;
-}
-constexpr int kTwoPass = 1000000;  // GemmPlan.splitk >= kTwoPass: two-pass split-K with S = splitk - kTwoPass slices (LDS-DMA kinds only); atomic split counts stay far below
 inline int twopass_ldws(int N) { return (N + 3) & ~3; }
-// eligibility of the two-pass split for this call: plain row-major single-batch output and enough caller scratch for S slices
-// (smax: the tuned two-pass plans stop at 4 slices; the ordered slab split of the deterministic mode keeps the slice count of the atomic plan it replaces)
-inline bool twopass_ok(const GemmEpi& ep, int M, int N, int batch, int S, int smax = 4) {
-    return ep.sk_ws && batch == 1 && ep.ldcj == 1 && (ep.mode == 0 || ep.mode == 1) && S >= 2 && S <= smax && (long)S * M * twopass_ldws(N) <= ep.sk_ws_floats;
+// the epilogue of the k-slices of a two-pass / slab split: raw partial sums [M][ldws] into the caller's scratch, no statistics; the epilogue proper
+// runs in the fix-up pass
+inline GemmEpi slice_epilogue(const GemmEpi& ep, int M, int N) {
+    GemmEpi e = ep;
+    const int ldws = twopass_ldws(N);
+    e.C = ep.sk_ws; e.ldc = ldws; e.ldcj = 1; e.sc_outer = e.sc_inner = 0; e.inner = 1; e.bias = nullptr; e.res = nullptr;
+    e.mask = nullptr; e.alpha = 1.f; e.relu = 0; e.mode = 0; e.sk_stride = (long)M * ldws;
+    e.drop_seed = nullptr; e.stat = nullptr;
+    return e;
 }
-// Deterministic mode (tf_set_deterministic): k-slices of the ORDERED SLAB split that replaces a plan's atomic k-split - slice s stores its raw
-// partial tile at sk_ws + s * M * ldws with plain stores, launch_splitk_fixup adds the slices to C in slice order.  The plan's own slice count,
-// lowered until the caller's scratch holds that many slices; 1 (unsplit) without scratch, for batched calls and column-strided outputs.
-constexpr int kSlabMax = 1 << 16;
 // the register-staged slab kernels (gemm_slab_kernel) are instantiated for the weight-gradient layouts only - both operands stored with the contraction
 // index as their row ([tn] GEMMs, the implicit-GEMM convolution weight gradients): every k-split plan of the train step has this layout; an
 // accumulating call of another layout runs unsplit in the deterministic mode
 template <bool A_KC, bool B_KC> constexpr bool kSlabLayout = !A_KC && !B_KC;
-inline int slab_slices(const GemmEpi& ep, int M, int N, int batch, int splitk) {
-    if (!ep.sk_ws || batch != 1 || ep.ldcj != 1 || ep.mode != 1 || splitk < 2) return 1;
-    const long fit = ep.sk_ws_floats / ((long)M * twopass_ldws(N));
-    const long S = splitk < fit ? splitk : fit;
-    return S < 2 ? 1 : (int)(S < kSlabMax ? S : kSlabMax);
-}
 
 // pair launch (gemm_pair.cpp): between tf_gemm_pair_begin() and tf_gemm_pair_end() up to two eligible GEMMs are held back and launched as ONE grid
 bool pair_capturing();
@@ -913,45 +896,35 @@ void plan_store(const char* what, int M, int N, int K, int batch, int acc, const
 bool autotune_enabled();
 bool forced_plan(GemmPlan* out);   // tests: pin one tiling for every call
 
-inline int heuristic_splitk(int M, int N, int K, int batch, int bm, int bn, int bk) {
-    const long tiles = (long)cdiv(M, bm) * cdiv(N, bn) * batch;
-    const int ktiles = cdiv(K, bk);
-    if (tiles >= 512 || ktiles * bk < 256) return 1;
-    long want = (1024 + tiles - 1) / tiles;
-    long maxs = (long)ktiles * bk / 128;
-    if (want > maxs) want = maxs;
-    return want < 1 ? 1 : (int)want;
+// ---- the plan of one call (gemm_plan.cpp).  PlanCall is everything the choice of kernel and k-partition depends on; resolve_plan() is the only
+// place that makes that choice, for the launch (launch_gemm) and for the scratch queries of the sites (plan_scratch_floats) alike.
+struct PlanCall {
+    const char* site; int M, N, K, batch;
+    bool allow_splitk;             // the site may split K (weight gradients)
+    bool slab_layout;              // kSlabLayout: the register-staged slab kernels exist for this operand layout
+    bool dma_ok;                   // plain operands that the LDS-DMA kernels can take (dma_eligible)
+    int mode; bool bias, res, relu, mask, stat; long ldcj;       // the epilogue facts the rules read
+    bool ws, flags; long ws_floats;                              // caller scratch / stream-K hand-over flags of this call
+};
+inline PlanCall plan_call(const char* site, int M, int N, int K, int batch, bool allow_splitk, bool slab_layout, bool dma_ok, const GemmEpi& ep) {
+    return {site, M, N, K, batch, allow_splitk, slab_layout, dma_ok, ep.mode, ep.bias != nullptr, ep.res != nullptr, ep.relu != 0, ep.mask != nullptr,
+            ep.stat != nullptr, ep.ldcj, ep.sk_ws != nullptr, ep.sk_flags != nullptr, ep.sk_ws_floats};
 }
-
-// Heuristic tile choice (used when no tuned plan exists): smallest BN that covers N with the least padding,
-// BM=64 when the grid would not fill the 256 CUs, split-K (atomic epilogue) for skinny outputs with deep reductions.
-inline GemmPlan plan_gemm(int M, int N, int K, int batch, bool allow_splitk) {
-    GemmPlan p;
-    if (N <= 32) p.bn = 32;
-    else if (N <= 64) p.bn = 64;
-    else if (N <= 96) p.bn = 96;
-    else {
-        const long w128 = (long)cdiv(N, 128) * 128, w96 = (long)cdiv(N, 96) * 96;
-        p.bn = (w96 < w128) ? 96 : 128;
-    }
-    p.bm = 128;
-    p.bk = 16;
-    const long t128 = (long)cdiv(M, 128) * cdiv(N, p.bn) * batch;
-    if ((p.bn == 128 || p.bn == 64) && t128 < 384 && M > 64) p.bm = 64;
-    p.splitk = allow_splitk ? heuristic_splitk(M, N, K, batch, p.bm, p.bn, p.bk) : 1;
-    return p;
-}
-
-// Deterministic mode: scratch floats the ordered slab k-split of a pure accumulation (batch 1, row-major output) at site `what` wants - the plan
-// launch_gemm will pick for it under the flag (pinned, cached or heuristic: never tuned) times one [M][ldws] slice per k-slice; 0 = the plan does
-// not split K atomically.
-inline long slab_ws_floats(const char* what, int M, int N, int K) {
-    GemmPlan p;
-    const int acc = 2 + 4 * (gemm_precision() == 3 ? 1 : gemm_precision());
-    if (!forced_plan(&p) && !plan_lookup(what, M, N, K, 1, acc, &p)) p = plan_gemm(M, N, K, 1, true);
-    if (p.splitk < 2 || p.splitk >= kTwoPass) return 0;
-    return (long)(p.splitk < kSlabMax ? p.splitk : kSlabMax) * M * twopass_ldws(N);
-}
+struct ResolvedPlan {
+    GemmPlan plan;                 // final tile, kind and k-partition
+    long ws_floats;                // caller scratch that partition uses
+    bool stat;                     // the fused output statistics survive (else the caller gets nparts = 0)
+    bool atomic;                   // the epilogue mode becomes 2 (float atomics)
+    bool sk_ok;                    // a pure accumulation: the call may split K
+    bool tune;                     // no pinned / cached plan and the autotuner is on: `plan` is the heuristic one until autotune_gemm has stored its winner
+};
+ResolvedPlan resolve_plan(const PlanCall& c);
+void store_tuned_plan(const PlanCall& c, const GemmPlan& p);
+long plan_scratch_floats(PlanCall c);        // what the call would use if it brought scratch (and flags): the answer of the sites' *_ws_floats queries
+bool twopass_ok(const PlanCall& c, int S, int smax = 4);
+int streamk_blocks(const PlanCall& c, const DmaKindInfo& ki);
+int heuristic_splitk(int M, int N, int K, int batch, int bm, int bn, int bk);
+GemmPlan plan_gemm(int M, int N, int K, int batch, bool allow_splitk);
 
 // 16-byte epilogue on a transposed accumulator (GemmEpi::trn, gemm_epilogue_t).  TF_GEMM_EPI16=0 keeps every launch on the 4-byte epilogue.
 int gemm_epi16();                  // api.cpp: the switch (read once from the environment; tf_gemm_epi16 re-sets it for tests)
@@ -971,6 +944,17 @@ inline bool epi16_eligible(const GemmEpi& ep, int N, int BM, int BN, int WAVES_M
     return true;
 }
 
+// tile rasterisation (GemmEpi::group_m): as many tile-rows as keep their A panels (BM rows x kpanel floats of this launch) in ~half the L2
+// (forced: TF_GROUP_M, register-staged launches only)
+inline int raster_group_m(int BM, int kpanel, int tiles_m, int tiles_n, int forced = 0) {
+    const long panel = (long)BM * kpanel * 4;
+    int g = (int)((2L << 20) / (panel > 0 ? panel : 1));
+    if (g > 8) g = 8;
+    if (forced > 0) g = forced;
+    if (g > tiles_m) g = tiles_m;
+    return (g >= 2 && tiles_n >= 4) ? g : 1;
+}
+
 // grid geometry + launch-time epilogue fields (compute precision, tile rasterisation, number of statistic parts) of one register-staged launch
 struct CfgGeom { int tiles_m, tiles_n, kchunk, nsplit; GemmEpi epg; };
 inline CfgGeom cfg_geom(const GemmEpi& ep, int M, int N, int K, int splitk, int BM, int BN, int BK, int WAVES_M, bool allvec = true) {
@@ -984,15 +968,8 @@ inline CfgGeom cfg_geom(const GemmEpi& ep, int M, int N, int K, int splitk, int 
     c.epg = ep;
     c.epg.prec = gemm_precision();
     { static const int dbg = [] { const char* e = getenv("TF_GEMM_DBG"); return e ? atoi(e) : 0; }(); c.epg.prec |= dbg << 8; }      // timing diagnosis (tools/pair_lab.py): bit 8 = no epilogue stores, results are garbage
-    {
-        static const int forced = [] { const char* e = getenv("TF_GROUP_M"); return e ? atoi(e) : 0; }();
-        long panel = (long)BM * (kchunk < K ? kchunk : K) * 4;          // bytes of one A panel of this launch
-        int g = (int)((2L << 20) / (panel > 0 ? panel : 1));            // as many tile-rows as keep their A panels in ~half the L2
-        if (g > 8) g = 8;
-        if (forced > 0) g = forced;
-        if (g > c.tiles_m) g = c.tiles_m;
-        c.epg.group_m = (g >= 2 && c.tiles_n >= 4) ? g : 1;
-    }
+    static const int forced_group_m = [] { const char* e = getenv("TF_GROUP_M"); return e ? atoi(e) : 0; }();
+    c.epg.group_m = raster_group_m(BM, kchunk < K ? kchunk : K, c.tiles_m, c.tiles_n, forced_group_m);
     if (c.epg.stat_nparts) *c.epg.stat_nparts = c.epg.stat ? cdiv(M, BM / WAVES_M) : 0;
     c.epg.trn = epi16_eligible(c.epg, N, BM, BN, WAVES_M, allvec) ? 1 : 0;
     if (c.epg.trn) epi16_count(1);
@@ -1001,16 +978,13 @@ inline CfgGeom cfg_geom(const GemmEpi& ep, int M, int N, int K, int splitk, int 
 }
 
 template <int BM, int BN, int WAVES_M, int BK, class LA, bool A_KC, class LB, bool B_KC, int NT = 256, int PF = 1>
-inline void launch_cfg(const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, int splitk, void* stream, bool slab = false) {
+inline void launch_cfg(const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, KSplit split, int slices, void* stream) {
+    // the register-staged kernels know two partitions: atomic k-slices (the caller's epilogue has mode 2) and the ordered slab split (batch 1)
+    const bool slab = split == KSplit::Slab && kSlabLayout<A_KC, B_KC>;
     GemmEpi eps = ep;
     const int ldws = twopass_ldws(N);
-    slab = slab && kSlabLayout<A_KC, B_KC>;
-    if (slab) {         // ordered slab k-split (batch 1): the slices store raw partial sums [M][ldws] into the caller's scratch, the epilogue proper runs in the fix-up pass
-        eps.C = ep.sk_ws; eps.ldc = ldws; eps.ldcj = 1; eps.sc_outer = eps.sc_inner = 0; eps.inner = 1; eps.bias = nullptr; eps.res = nullptr;
-        eps.mask = nullptr; eps.alpha = 1.f; eps.relu = 0; eps.mode = 0; eps.sk_stride = (long)M * ldws;
-        eps.drop_seed = nullptr; eps.stat = nullptr; eps.stat_nparts = nullptr;
-    }
-    const CfgGeom cg = cfg_geom(eps, M, N, K, splitk, BM, BN, BK, WAVES_M, la.vec && lb.vec);
+    if (slab) { eps = slice_epilogue(ep, M, N); eps.stat_nparts = nullptr; }
+    const CfgGeom cg = cfg_geom(eps, M, N, K, (slab || split == KSplit::Atomic) ? slices : 1, BM, BN, BK, WAVES_M, la.vec && lb.vec);
     const int tiles_m = cg.tiles_m, tiles_n = cg.tiles_n, kchunk = cg.kchunk;
     dim3 grid(tiles_m * tiles_n, cg.nsplit, batch);
     const GemmEpi& epg = cg.epg;
@@ -1031,19 +1005,18 @@ inline void launch_cfg(const LA& la, const LB& lb, const GemmEpi& ep, int M, int
 }
 
 template <class LA, bool A_KC, class LB, bool B_KC>
-inline void launch_plan(const GemmPlan& p, const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, void* stream, int slab = 0) {
-    // slab >= 2: the ordered slab k-split of the deterministic mode with that many slices (slab_slices): the LDS-DMA kernels run it as their two-pass split
-    if constexpr (std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value) {
+inline void launch_plan(const GemmPlan& p, const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, void* stream) {
+    constexpr bool plain = std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value;
+    if constexpr (plain) {
         if (p.kind >= 1 && p.kind <= kDmaKinds && dma_eligible(la, lb)) {
-            launch_dma_plan<A_KC, B_KC>(p.kind, la, lb, ep, M, N, K, batch, slab ? kTwoPass + slab : p.splitk, stream);
+            launch_dma_plan<A_KC, B_KC>(p.kind, la, lb, ep, M, N, K, batch, p.split, p.slices, stream);
             return;
         }
     }
-    const int sk = slab ? slab : (p.splitk >= kTwoPass ? 1 : p.splitk);       // the tuned two-pass plans exist in the LDS-DMA kernels only
 #define TF_CFG(BM_, BN_, WM_)                                                                                      \
     do {                                                                                                           \
-        if (p.bk == 32) launch_cfg<BM_, BN_, WM_, 32, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk, stream, slab != 0); \
-        else launch_cfg<BM_, BN_, WM_, 16, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk, stream, slab != 0);       \
+        if (p.bk == 32) launch_cfg<BM_, BN_, WM_, 32, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, p.split, p.slices, stream); \
+        else launch_cfg<BM_, BN_, WM_, 16, LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, p.split, p.slices, stream);       \
     } while (0)
     if (p.bm == 128) {
         if (p.bn == 32) TF_CFG(128, 32, 4);
@@ -1063,7 +1036,7 @@ inline void launch_plan(const GemmPlan& p, const LA& la, const LB& lb, const Gem
 inline bool trace_tune() { static const bool on = [] { const char* e = getenv("TF_TRACE_TUNE"); return e && atoi(e) != 0; }(); return on; }
 inline void trace_candidate(const GemmPlan& p, int M, int N, int K, int batch, int mode, void* stream, bool before) {
     if (!trace_tune()) return;
-    if (before) fprintf(stderr, "[tune] %dx%dx%d batch %d: tile %dx%dx%d splitk %d kind %d mode %d ...", M, N, K, batch, p.bm, p.bn, p.bk, p.splitk, p.kind, mode);
+    if (before) fprintf(stderr, "[tune] %dx%dx%d batch %d: tile %dx%dx%d split %d x %d kind %d mode %d ...", M, N, K, batch, p.bm, p.bn, p.bk, (int)p.split, p.slices, p.kind, mode);
     else { hipError_t e = hipStreamSynchronize((hipStream_t)stream); fprintf(stderr, " %s\n", e == hipSuccess ? "ok" : hipGetErrorString(e)); }
     fflush(stderr);
 }
@@ -1071,8 +1044,9 @@ inline void trace_candidate(const GemmPlan& p, int M, int N, int K, int batch, i
 // problem ONCE with HIP events during eager warm-up; the winner goes into the plan cache.  Trial launches of
 // accumulating epilogues write into a scratch copy of the destination extent, so the live accumulator is left unchanged.
 template <class LA, bool A_KC, class LB, bool B_KC>
-inline GemmPlan autotune_gemm(const LA& la, const LB& lb, const GemmEpi& ep, int M, int N, int K, int batch, bool allow_splitk, void* stream) {
+inline GemmPlan autotune_gemm(const LA& la, const LB& lb, const GemmEpi& ep, const PlanCall& c, bool allow_splitk, void* stream) {
     static const int tiles[6][2] = {{128, 128}, {128, 96}, {128, 64}, {128, 32}, {64, 128}, {64, 64}};
+    const int M = c.M, N = c.N, K = c.K, batch = c.batch;
     GemmEpi trial = ep;
     float* trial_scratch = nullptr;
     if (ep.mode != 0) {
@@ -1092,76 +1066,49 @@ inline GemmPlan autotune_gemm(const LA& la, const LB& lb, const GemmEpi& ep, int
     hipEventCreate(&e0); hipEventCreate(&e1);
     GemmPlan best = plan_gemm(M, N, K, batch, allow_splitk);
     float best_ms = 1e30f;
+    // one candidate: a warm launch, then the best of three groups of 4 launches (one noisy group must not decide a plan)
+    auto time_plan = [&](const GemmPlan& p) {
+        GemmEpi e = trial;
+        if (p.split == KSplit::Atomic) { if (ep.mode == 0) return; e.mode = 2; }
+        trace_candidate(p, M, N, K, batch, e.mode, stream, true);
+        launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, e, M, N, K, batch, stream);
+        trace_candidate(p, M, N, K, batch, e.mode, stream, false);
+        float ms = 1e30f;
+        for (int pass = 0; pass < 3; ++pass) {
+            hipEventRecord(e0, (hipStream_t)stream);
+            for (int r = 0; r < 4; ++r) launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, e, M, N, K, batch, stream);
+            hipEventRecord(e1, (hipStream_t)stream);
+            hipEventSynchronize(e1);
+            float t = 0.f;
+            hipEventElapsedTime(&t, e0, e1);
+            if (t < ms) ms = t;
+        }
+        if (ms < best_ms) { best_ms = ms; best = p; }
+    };
+    // atomic k-splits worth trying for a tile: none, the heuristic count and (from 4 up) half of it
+    auto time_atomic_splits = [&](int bm, int bn, int bk, int kind) {
+        time_plan(atomic_plan(bm, bn, bk, kind, 1));
+        const int h = allow_splitk ? heuristic_splitk(M, N, K, batch, bm, bn, bk) : 1;
+        if (h > 1) { time_plan(atomic_plan(bm, bn, bk, kind, h)); if (h >= 4) time_plan(atomic_plan(bm, bn, bk, kind, h / 2)); }
+    };
     const int npad = cdiv(N, 32) * 32;
     for (int t = 0; t < 6; ++t) {
         const int bm = tiles[t][0], bn = tiles[t][1];
         if (bn > 32 && bn >= npad + 32) continue;          // a whole extra 32-column strip of padding
         if (bm == 64 && M <= 64 && t != 4 && t != 5) continue;
-        for (int bk = 16; bk <= 32; bk += 16) {
-            int sks[3] = {1, 0, 0}, nsk = 1;
-            if (allow_splitk) {
-                const int h = heuristic_splitk(M, N, K, batch, bm, bn, bk);
-                if (h > 1) { sks[nsk++] = h; if (h >= 4) sks[nsk++] = h / 2; }
-            }
-            for (int s = 0; s < nsk; ++s) {
-                GemmPlan p{bm, bn, bk, sks[s], 0};
-                GemmEpi e = trial;
-                if (p.splitk > 1) { if (ep.mode == 0) continue; e.mode = 2; }
-                trace_candidate(p, M, N, K, batch, e.mode, stream, true);
-                launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, e, M, N, K, batch, stream);   // warm
-                trace_candidate(p, M, N, K, batch, e.mode, stream, false);
-                float ms = 1e30f;
-                for (int pass = 0; pass < 3; ++pass) {     // best of three groups of 4 launches: one noisy group must not decide a plan
-                    hipEventRecord(e0, (hipStream_t)stream);
-                    for (int r = 0; r < 4; ++r) launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, e, M, N, K, batch, stream);
-                    hipEventRecord(e1, (hipStream_t)stream);
-                    hipEventSynchronize(e1);
-                    float t = 0.f;
-                    hipEventElapsedTime(&t, e0, e1);
-                    if (t < ms) ms = t;
-                }
-                if (ms < best_ms) { best_ms = ms; best = p; }
-            }
-        }
+        for (int bk = 16; bk <= 32; bk += 16) time_atomic_splits(bm, bn, bk, 0);
     }
-    if constexpr (std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value) {
-        if (dma_eligible(la, lb)) {
-            for (int kind = 1; kind <= kDmaKinds; ++kind) {
-                const DmaKindInfo ki = dma_kind_info(kind);
-                if (ki.bn > 32 && ki.bn >= npad + 32) continue;
-                if (ki.bm > 64 && M <= 64) continue;
-                int sks[3] = {1, 0, 0}, nsk = 1;
-                if (allow_splitk) {
-                    const int h = heuristic_splitk(M, N, K, batch, ki.bm, ki.bn, ki.bk);
-                    if (h > 1) { sks[nsk++] = h; if (h >= 4) sks[nsk++] = h / 2; }
-                }
-                int cand[8], nc = 0;
-                for (int s = 0; s < nsk; ++s) cand[nc++] = sks[s];
-                if ((long)cdiv(M, ki.bm) * cdiv(N, ki.bn) < 512 && K >= 32 * ki.bk)      // too few tiles for the 256 CUs: deterministic two-pass split
-                    for (int S = 2; S <= 4; ++S)
-                        if (twopass_ok(ep, M, N, batch, S)) cand[nc++] = kTwoPass + S;
-                if (streamk_blocks(ep, M, N, K, batch, ki.bm, ki.bn, ki.bk, ki.nw, ki.occ, ki.lds) > 0) cand[nc++] = kStreamK;      // tile count does not divide over the resident slots
-                for (int s = 0; s < nc; ++s) {
-                    GemmPlan p{ki.bm, ki.bn, ki.bk, cand[s], kind};
-                    GemmEpi e = trial;
-                    if (p.splitk > 1 && p.splitk < kTwoPass) { if (ep.mode == 0) continue; e.mode = 2; }
-                    if (p.splitk == kStreamK && e.mode == 2) continue;
-                    trace_candidate(p, M, N, K, batch, e.mode, stream, true);
-                    launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, e, M, N, K, batch, stream);
-                    trace_candidate(p, M, N, K, batch, e.mode, stream, false);
-                    float ms = 1e30f;
-                    for (int pass = 0; pass < 3; ++pass) {
-                        hipEventRecord(e0, (hipStream_t)stream);
-                        for (int r = 0; r < 4; ++r) launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, e, M, N, K, batch, stream);
-                        hipEventRecord(e1, (hipStream_t)stream);
-                        hipEventSynchronize(e1);
-                        float t = 0.f;
-                        hipEventElapsedTime(&t, e0, e1);
-                        if (t < ms) ms = t;
-                    }
-                    if (ms < best_ms) { best_ms = ms; best = p; }
-                }
-            }
+    if (c.dma_ok) {
+        for (int kind = 1; kind <= kDmaKinds; ++kind) {
+            const DmaKindInfo ki = dma_kind_info(kind);
+            if (ki.bn > 32 && ki.bn >= npad + 32) continue;
+            if (ki.bm > 64 && M <= 64) continue;
+            time_atomic_splits(ki.bm, ki.bn, ki.bk, kind);
+            if ((long)cdiv(M, ki.bm) * cdiv(N, ki.bn) < 512 && K >= 32 * ki.bk)      // too few tiles for the 256 CUs: deterministic two-pass split
+                for (int S = 2; S <= 4; ++S)
+                    if (twopass_ok(c, S)) time_plan(GemmPlan{ki.bm, ki.bn, ki.bk, kind, KSplit::TwoPass, S});
+            const int P = streamk_blocks(c, ki);           // > 0: the tile count does not divide over the resident slots
+            if (P > 0) time_plan(GemmPlan{ki.bm, ki.bn, ki.bk, kind, KSplit::StreamK, P});
         }
     }
     hipEventDestroy(e0); hipEventDestroy(e1);
@@ -1174,62 +1121,29 @@ template <class LA, bool A_KC, class LB, bool B_KC>
 inline int launch_gemm(const LA& la, const LB& lb, GemmEpi ep, int M, int N, int K, int batch, bool allow_splitk, void* stream,
                        const char* what) {
     if (M <= 0 || N <= 0 || batch <= 0) return 0;
-    // split-K only for pure accumulations (weight gradients into the grad arena): atomic epilogue
-    const bool sk_ok = allow_splitk && ep.mode == 1 && !ep.bias && !ep.res && !ep.relu;
-    const int acc = (ep.mode != 0 ? (sk_ok ? 2 : 1) : 0) + 4 * (gemm_precision() == 3 ? 1 : gemm_precision());   // plans are tuned per compute precision (fp16 shares the bf16 plans)
-    const bool det = deterministic();     // tf_set_deterministic: no atomic k-split, no tuning (the plan cache records nothing found under the flag)
-    GemmPlan p;
-    if (forced_plan(&p)) {
-        if (!sk_ok && p.splitk < kTwoPass) p.splitk = 1;
-    } else if (!plan_lookup(what, M, N, K, batch, acc, &p)) {
+    constexpr bool plain = std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value;
+    bool dma_ok = false;
+    if constexpr (plain) dma_ok = dma_eligible(la, lb);
+    const PlanCall c = plan_call(what, M, N, K, batch, allow_splitk, kSlabLayout<A_KC, B_KC>, dma_ok, ep);
+    ResolvedPlan r = resolve_plan(c);
 #ifndef TF_EMU
-        if (autotune_enabled() && !det) {
-            p = autotune_gemm<LA, A_KC, LB, B_KC>(la, lb, ep, M, N, K, batch, sk_ok, stream);
-            plan_store(what, M, N, K, batch, acc, p);
-        } else
+    if (r.tune) {
+        store_tuned_plan(c, autotune_gemm<LA, A_KC, LB, B_KC>(la, lb, ep, c, r.sk_ok, stream));
+        r = resolve_plan(c);
+    }
 #endif
-            p = plan_gemm(M, N, K, batch, sk_ok);
-    }
-    bool streamk = p.splitk == kStreamK;
-    if (streamk) {      // stream-K plan: needs an LDS-DMA kind, this call's scratch + flags and a tile count that does not divide over the slots
-        bool ok = false;
-        if constexpr (std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value) {
-            const DmaKindInfo ki = dma_kind_info(p.kind);
-            ok = p.kind >= 1 && p.kind <= kDmaKinds && dma_eligible(la, lb) && streamk_blocks(ep, M, N, K, batch, ki.bm, ki.bn, ki.bk, ki.nw, ki.occ, ki.lds) > 0;
-        }
-        if (!ok) { p.splitk = 1; streamk = false; }
-    }
-    if (ep.stat && streamk) {
-        if (ep.mode != 0 || ep.res || ep.relu || ep.mask) ep.stat = nullptr;      // the owner of a cut tile holds the complete sum: statistics as usual
-        if (!ep.stat && ep.stat_nparts) *ep.stat_nparts = 0;
-    } else if (ep.stat) {
-        // fused output statistics need the whole reduction in one block: no k-split.  A cached two-pass plan keeps its speed and reports
-        // "no statistics" (nparts 0): the caller runs its separate reduction for this (rare: <= 256-tile) output
-        if (p.splitk >= kTwoPass && p.kind >= 1 && twopass_ok(ep, M, N, batch, p.splitk - kTwoPass)) ep.stat = nullptr;
-        else if (p.splitk > 1) p.splitk = 1;
-        if (ep.mode != 0 || ep.res || ep.relu || ep.mask) ep.stat = nullptr;
-        if (!ep.stat && ep.stat_nparts) *ep.stat_nparts = 0;
-    }
-    int slab = 0;
-    if (streamk) {
-    } else if (p.splitk >= kTwoPass) {
-        if (p.kind < 1 || !twopass_ok(ep, M, N, batch, p.splitk - kTwoPass)) p.splitk = 1;     // no scratch on this call / not a plain output
-    } else {
-        if (!sk_ok) p.splitk = 1;
-        if (p.splitk > 1 && det) {          // the plan's tile and slice count, the slices combined in slice order through the caller's scratch
-            slab = kSlabLayout<A_KC, B_KC> ? slab_slices(ep, M, N, batch, p.splitk) : 1;
-            if (slab < 2) { slab = 0; p.splitk = 1; }
-            else slab_splitk_count(1);
-        } else if (p.splitk > 1) ep.mode = 2;
-    }
-    if constexpr (std::is_same<LA, PlainOp>::value && std::is_same<LB, PlainOp>::value) {
+    const GemmPlan& p = r.plan;
+    if (ep.stat && !r.stat) { ep.stat = nullptr; if (ep.stat_nparts) *ep.stat_nparts = 0; }
+    if (r.atomic) ep.mode = 2;
+    if constexpr (plain) {
         // tf_gemm_pair_begin(): a 64 x 64-tile register-staged launch with vector operands is held back so that tf_gemm_pair_end() can put
         // it into one grid with its partner (gemm_pair.cpp); anything else launches right here, as always
-        if (!det && pair_capturing() && p.kind == 0 && p.bm == 64 && p.bn == 64 && (p.bk == 16 || p.bk == 32) && p.splitk < kTwoPass && batch == 1 && la.vec && lb.vec &&
+        if (!deterministic() && pair_capturing() && p.kind == 0 && p.bm == 64 && p.bn == 64 && (p.bk == 16 || p.bk == 32) && batch == 1 && la.vec && lb.vec &&
             !ep.stat && pair_hold(la, lb, ep, M, N, K, A_KC, B_KC, p, what))
             return 0;
     }
-    launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, ep, M, N, K, batch, stream, slab);
+    launch_plan<LA, A_KC, LB, B_KC>(p, la, lb, ep, M, N, K, batch, stream);
+    if (p.split == KSplit::Slab) slab_splitk_count(1);
     return launch_status(what);
 }
 
