@@ -335,7 +335,9 @@ int tf_softmax_dropout_bwd_f32(const float* p, float* dp, int rows, int n, int l
  * columns h*hs .. (h+1)*hs of each third; y: (B*T, C) heads merged (transfuser.py:523); lse: (B*nh*T) row-wise log-sum-exp kept for the
  * backward, which RECOMPUTES the probabilities.  attn_drop mask = tf_dropout_f32's for the flat index ((b nh + h) T + i) Tp + j, Tp = T
  * rounded up to 4 (pdrop = 0: no dropout, seed_dev may be NULL).  bwd: dqkv (B*T, 3C) = gradients of [key | query | value]; dsum: (B*nh*T)
- * scratch.  Limits: T <= 192, hs <= 384 (tf_attention_supported); the model has T = 174, hs in {18, 54, 144, 378}. */
+ * scratch.  Limits: T <= 1024, even hs <= 384 (tf_attention_supported); the model has T = 174, hs in {18, 54, 144, 378}.  T <= 192 (one column
+ * chunk) runs the whole-row kernels; 192 < T <= 1024 (other anchor grids, transfuser.py:19-20,304) the column-chunked ones, dispatched inside
+ * tf_attention_fwd_f32 and tf_attention_bwd_y_f32.  tf_attention_bwd_f32 (the two dependent launches without y) stays at T <= 192 and fails beyond. */
 int tf_attention_supported(int T, int C, int nh);
 int tf_attention_fwd_f32(const float* qkv, float* y, float* lse, int B, int T, int C, int nh, const uint32_t* seed_dev, uint32_t site, float pdrop,
                          void* stream);

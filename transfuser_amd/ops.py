@@ -1012,7 +1012,7 @@ def attention_bwd(qkv, dy, lse, B, T, C, nh, drop=None, y=None):
     dqkv = torch.empty_like(qkv)
     dsum = torch.empty_like(lse)
     seed, site, p = drop if drop is not None else (None, 0, 0.0)
-    if y is not None and ATT_BWD_ONE:
+    if y is not None and (ATT_BWD_ONE or T > 192):      # beyond one column chunk (T > 192) only the one-grid form exists
         check(L().tf_attention_bwd_y_f32(ptr(_c(qkv)), ptr(_c(dy)), ptr(_c(y)), ptr(lse), ptr(dqkv), ptr(dsum), B, T, C, nh, ptr(seed), ctypes.c_uint32(site),
                                          ctypes.c_float(p), stream_of(qkv)), "tf_attention_bwd_y_f32")
         return dqkv
