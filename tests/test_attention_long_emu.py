@@ -3,11 +3,14 @@ tests/test_attention_long_gpu.py (shared cases in tests/attention_long_cases.py)
 import pytest
 
 import attention_long_cases as alc
+import kernel_cases as kc
+import redzone
+from transfuser_amd import ops
 
 
 @pytest.fixture(autouse=True)
-def _backend(emu_backend):
-    yield
+def _backend(emu_backend, request):
+    yield from redzone.fixture_guard(request, ops, alc, kc)      # guard bands + NaN poison around every tensor ops / the cases allocate
 
 
 @pytest.mark.parametrize("case", alc.PARITY_CASES, ids=str)

@@ -8,6 +8,8 @@ import sys
 import pytest
 
 import determinism_cases as dc
+import kernel_cases as kc
+import redzone
 from transfuser_amd import ops
 
 DEV = "cpu"
@@ -15,12 +17,14 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
 @pytest.fixture(autouse=True)
-def _backend(emu_backend):
+def _backend(emu_backend, request):
     prev = ops.is_deterministic()
-    yield
-    ops.set_deterministic(prev)
-    ops.force_plan(0)
-    ops.gemm_epi16(None)
+    try:
+        yield from redzone.fixture_guard(request, ops, dc, kc)      # guard bands + NaN poison around every tensor ops / the cases allocate
+    finally:
+        ops.set_deterministic(prev)
+        ops.force_plan(0)
+        ops.gemm_epi16(None)
 
 
 def test_flag_round_trip():

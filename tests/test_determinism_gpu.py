@@ -6,19 +6,24 @@ import torch
 
 import determinism_cases as dc
 import kernel_cases as kc
+import redzone
 from transfuser_amd import ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+CAPTURES_A_GRAPH = ("test_train_step_bitwise_regnet[graph]",)      # outside the guard
 
 
 @pytest.fixture(autouse=True)
-def _flag_restored():
+def _gpu(request):
     prev = ops.is_deterministic()
-    yield
-    ops.set_deterministic(prev)
-    ops.force_plan(0)
-    ops.gemm_epi16(None)
+    try:
+        yield from redzone.fixture_guard(request, ops, dc, kc, outside=CAPTURES_A_GRAPH)      # guard bands + NaN poison around every tensor ops / the cases allocate
+        torch.cuda.synchronize()
+    finally:
+        ops.set_deterministic(prev)
+        ops.force_plan(0)
+        ops.gemm_epi16(None)
 
 
 # 1. engine k-split, plain

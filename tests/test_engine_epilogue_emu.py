@@ -3,11 +3,14 @@ MFMA's lane layout, so the same cases as tests/test_engine_epilogue_gpu.py run o
 import pytest
 
 import epilogue_cases as ec
+import kernel_cases as kc
+import redzone
+from transfuser_amd import ops
 
 
 @pytest.fixture(autouse=True)
-def _backend(emu_backend):
-    yield
+def _backend(emu_backend, request):
+    yield from redzone.fixture_guard(request, ops, ec, kc)      # guard bands + NaN poison around every tensor ops / the cases allocate
 
 
 @pytest.mark.parametrize("plan", ec.PLANS, ids=str)

@@ -5,11 +5,13 @@ import pytest
 import torch
 
 import kernel_cases as kc
+import redzone
+from transfuser_amd import ops
 
 
 @pytest.fixture(autouse=True)
-def _backend(emu_backend):
-    yield
+def _backend(emu_backend, request):
+    yield from redzone.fixture_guard(request, ops, kc)      # guard bands + NaN poison around every tensor ops / the cases allocate
 
 
 @pytest.mark.parametrize("case", kc.GEMM_CASES, ids=str)

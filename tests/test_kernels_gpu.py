@@ -3,19 +3,22 @@ against a plain PyTorch fp32 reference / the CPU oracle.  Same cases as tests/te
 import pytest
 import torch
 
+import dataprep_cases
 import kernel_cases as kc
+import redzone
+from transfuser_amd import ops
 
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True)
-def _gpu():
+def _gpu(request):
     assert torch.cuda.is_available(), "gpu tests need a GPU"
     from transfuser_amd import _lib
     assert not _lib.is_test_backend()
     _lib.load()  # raises if libtransfuser_hip.so is missing: no fallback
-    yield
+    yield from redzone.fixture_guard(request, ops, kc, dataprep_cases)      # guard bands + NaN poison around every tensor ops / the cases allocate
     torch.cuda.synchronize()
 
 
