@@ -496,6 +496,23 @@ int tf_adamw_scaled_f32(float* p, const float* g, float* m, float* v, int64_t n,
  * The next backward is seeded with ls_state[0].  No host synchronisation: hipGraph-capturable. */
 int tf_adamw_dynscale_f32(float* p, const float* g, float* m, float* v, int64_t n, float* state_dev, float beta1, float beta2, float eps,
                           float weight_decay, const float* g_check, int64_t n_check, float* ls_state, void* stream);
+/* Global-norm gradient clipping in front of the AdamW step (torch.nn.utils.clip_grad_norm_; extends the loop of train.py:305-314, which has
+ * none).  tf_grad_sumsq_f32 reads the 16-byte-aligned fp32 range g[0 .. n), n >= 1, once and stores P = tf_grad_sumsq_parts(n) <= 1024 partial
+ * sums of squares into `partials` (caller scratch of P floats; the library allocates nothing).  P depends on n alone, every block writes one
+ * plain store and nothing is combined with atomics: summing the partials in index order is a fixed-order sum, bitwise reproducible and legal
+ * under tf_set_deterministic(1). */
+int tf_grad_sumsq_parts(int64_t n);
+int tf_grad_sumsq_f32(const float* g, int64_t n, float* partials, void* stream);
+/* tf_adamw_scaled_f32 with the gradients clipped to `max_norm` on their way in (extends train.py:305-314 likewise): `partials` / `nparts` are
+ * what tf_grad_sumsq_f32 left for the norm range g_norm[0 .. n_norm) - the WHOLE active gradient arena, also when p / g / m / v are a ZeRO-1
+ * shard, as with g_check of tf_adamw_dynscale_f32.  Every block sums the partials in one fixed order, norm = gs * sqrt(sum),
+ * coef = min(1, max_norm / (norm + 1e-6)) - clip_grad_norm_'s formula, with its non-finite behaviour - and updates with gs * coef; the pre-clip
+ * norm (what clip_grad_norm_ returns) is stored to norm_out[0].  gs = grad_scale, or grad_scale / ls_state[0] with a (nullable) ls_state: the
+ * step then runs under the dynamic loss scale exactly as tf_adamw_dynscale_f32 does (overflow check over g_norm, which only this case reads;
+ * a skipped step writes nothing and does not count).  nparts must equal tf_grad_sumsq_parts(n_norm), max_norm > 0 (+inf never clips). */
+int tf_adamw_clip_f32(float* p, const float* g, float* m, float* v, int64_t n, float* state_dev, float beta1, float beta2, float eps, float weight_decay,
+                      float grad_scale, const float* g_norm, int64_t n_norm, const float* partials, int nparts, float max_norm, float* norm_out,
+                      float* ls_state, void* stream);
 /* lidar_to_histogram_features (data.py:446-470): points (B, max_points, stride>=3) f32 -> (B,2,256,256),
  * integer-exact; num_points may be NULL. */
 int tf_lidar_hist_f32(const float* points, const int32_t* num_points, int B, int max_points, int point_stride, float* out, void* stream);

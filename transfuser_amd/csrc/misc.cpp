@@ -84,12 +84,59 @@ __global__ void loss_scale_update_kernel(float* __restrict__ ls) {
     else if (++good >= ls[3]) { scale = fminf(scale * 2.0f, 16777216.0f); good = 0.f; }
     ls[0] = scale; ls[1] = good; ls[2] = 0.f;
 }
+// ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ in front of the optimizer step; the reference's loop, train.py:305-314, has
+// none).  Two launches and no pass that rewrites the gradients: grad_sumsq_kernel reads the norm range once and leaves ONE partial sum of squares
+// per block in caller scratch (a plain store - no atomics, the block count is a function of n alone, so the sum is a fixed-order sum on every
+// device); every block of the clipping instantiation of adamw_kernel re-reduces the <= kSumsqMaxParts partials in its prologue, all in the same
+// order (the pattern of pillars.cpp's second statistics pass: no finalize launch), and uses gs * coef where the plain one uses gs.
+constexpr int kSumsqMaxParts = 1024;
+inline int sumsq_parts(long n) {        // one block per 1024 floats (256 float4 lanes) up to the cap, then grid-stride trips
+    const long b = (n + 1023) / 1024;
+    return (int)(b < 1 ? 1 : (b > kSumsqMaxParts ? kSumsqMaxParts : b));
+}
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, long n4, long n, float* __restrict__ partials) {
+    __shared__ float red[4];
+    const long stride = (long)gridDim.x * 256;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;          // one accumulator per float4 component: n / (1024 P) sequential adds each
+    for (; i + 3 * stride < n4; i += 4 * stride) {         // four 16-byte loads in flight per thread and trip
+        const float4 a = reinterpret_cast<const float4*>(g)[i], b = reinterpret_cast<const float4*>(g)[i + stride];
+        const float4 c = reinterpret_cast<const float4*>(g)[i + 2 * stride], d = reinterpret_cast<const float4*>(g)[i + 3 * stride];
+        sx += a.x * a.x; sy += a.y * a.y; sz += a.z * a.z; sw += a.w * a.w;
+        sx += b.x * b.x; sy += b.y * b.y; sz += b.z * b.z; sw += b.w * b.w;
+        sx += c.x * c.x; sy += c.y * c.y; sz += c.z * c.z; sw += c.w * c.w;
+        sx += d.x * d.x; sy += d.y * d.y; sz += d.z * d.z; sw += d.w * d.w;
+    }
+    for (; i < n4; i += stride) {
+        const float4 a = reinterpret_cast<const float4*>(g)[i];
+        sx += a.x * a.x; sy += a.y * a.y; sz += a.z * a.z; sw += a.w * a.w;
+    }
+    for (long j = n4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; j < n; j += stride) sx += g[j] * g[j];      // scalar tail (< 4 elements)
+    const float t = block_sum<4>((sx + sy) + (sz + sw), red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+struct ClipArgs { const float* partials; int nparts; float max_norm; float* norm_out; };
+// adamw_kernel<> is the plain update (its parameter list and body are what they were before the clipping instantiation existed: the pack is empty
+// and the `if constexpr` blocks vanish); adamw_kernel<ClipArgs> takes one more argument and scales the gradients by the clip coefficient as well.
+template <class... CLIP>
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                     long n4, long n, const float* __restrict__ state, float b1, float b2, float eps, float wd, float gs,
-                                                    const float* __restrict__ ls = nullptr) {
+                                                    const float* __restrict__ ls, CLIP... clip) {
     if (ls) {                          // dynamic loss scale: ls = {scale, good steps, found_inf, growth interval}; an overflowed step is skipped as a whole
-        if (ls[2] != 0.f) return;
-        gs = 1.0f / ls[0];
+        if (ls[2] != 0.f) return;      // (nothing is written then, norm_out included)
+        if constexpr (sizeof...(CLIP) > 0) gs = gs / ls[0];      // the caller's scale (an accumulation window's 1 / k) composes with 1 / loss scale
+        else gs = 1.0f / ls[0];
+    }
+    if constexpr (sizeof...(CLIP) > 0) {
+        __shared__ float red[4];
+        const ClipArgs c = (clip, ...);
+        float s = 0.f;
+        for (int i = threadIdx.x; i < c.nparts; i += 256) s += c.partials[i];      // <= 4 terms per thread in index order, then the block tree: the
+        s = block_sum<4>(s, red);                                                   // same order in every block, so every block holds the same bits
+        const float norm = gs * sqrtf(s);
+        const float r = c.max_norm / (norm + 1e-6f);
+        gs *= r > 1.f ? 1.f : r;       // clamp(max = 1) as torch does it: a NaN norm stays a NaN coefficient, an infinite one gives 0
+        if (blockIdx.x == 0 && threadIdx.x == 0) c.norm_out[0] = norm;
     }
     const float step = state[0], lr = state[1];
     const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
@@ -287,7 +334,7 @@ extern "C" int tf_adamw_scaled_f32(float* p, const float* g, float* m, float* v,
     TF_REQUIRE(p && g && m && v && state_dev && n >= 0, "tf_adamw_f32: bad arguments");
     TF_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "tf_adamw_f32: arenas must be 16-byte aligned");
     TF_LAUNCH(adamw_tick_kernel, dim3(1), dim3(64), stream, state_dev, (const float*)nullptr);
-    if (n > 0) TF_LAUNCH(adamw_kernel, dim3(ew_blocks(n / 4 + 1, 8192)), dim3(256), stream, p, g, m, v, (long)(n / 4), (long)n, (const float*)state_dev,
+    if (n > 0) TF_LAUNCH(adamw_kernel<>, dim3(ew_blocks(n / 4 + 1, 8192)), dim3(256), stream, p, g, m, v, (long)(n / 4), (long)n, (const float*)state_dev,
                          beta1, beta2, eps, weight_decay, grad_scale, (const float*)nullptr);
     return launch_status("tf_adamw_f32");
 }
@@ -297,10 +344,32 @@ extern "C" int tf_adamw_dynscale_f32(float* p, const float* g, float* m, float* 
     TF_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!g_check || aligned16(g_check)), "tf_adamw_dynscale_f32: arenas must be 16-byte aligned");
     if (n_check > 0) TF_LAUNCH(grad_nonfinite_kernel, dim3(ew_blocks(n_check / 4 + 1, 8192)), dim3(256), stream, g_check, (long)(n_check / 4), (long)n_check, ls_state);
     TF_LAUNCH(adamw_tick_kernel, dim3(1), dim3(64), stream, state_dev, (const float*)ls_state);
-    if (n > 0) TF_LAUNCH(adamw_kernel, dim3(ew_blocks(n / 4 + 1, 8192)), dim3(256), stream, p, g, m, v, (long)(n / 4), (long)n, (const float*)state_dev,
+    if (n > 0) TF_LAUNCH(adamw_kernel<>, dim3(ew_blocks(n / 4 + 1, 8192)), dim3(256), stream, p, g, m, v, (long)(n / 4), (long)n, (const float*)state_dev,
                          beta1, beta2, eps, weight_decay, 1.0f, (const float*)ls_state);
     TF_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), stream, ls_state);
     return launch_status("tf_adamw_dynscale_f32");
+}
+extern "C" int tf_grad_sumsq_parts(int64_t n) { return sumsq_parts((long)n); }
+extern "C" int tf_grad_sumsq_f32(const float* g, int64_t n, float* partials, void* stream) {
+    TF_REQUIRE(g && partials && n >= 1, "tf_grad_sumsq_f32: bad arguments");
+    TF_REQUIRE(aligned16(g), "tf_grad_sumsq_f32: the range must be 16-byte aligned");
+    TF_LAUNCH(grad_sumsq_kernel, dim3(sumsq_parts((long)n)), dim3(256), stream, g, (long)(n / 4), (long)n, partials);
+    return launch_status("tf_grad_sumsq_f32");
+}
+extern "C" int tf_adamw_clip_f32(float* p, const float* g, float* m, float* v, int64_t n, float* state_dev, float beta1, float beta2, float eps,
+                                 float weight_decay, float grad_scale, const float* g_norm, int64_t n_norm, const float* partials, int nparts,
+                                 float max_norm, float* norm_out, float* ls_state, void* stream) {
+    TF_REQUIRE(p && g && m && v && state_dev && partials && norm_out && n >= 0 && n_norm >= 1 && (!ls_state || g_norm), "tf_adamw_clip_f32: bad arguments");
+    TF_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!g_norm || aligned16(g_norm)), "tf_adamw_clip_f32: arenas must be 16-byte aligned");
+    TF_REQUIRE(nparts == sumsq_parts((long)n_norm), "tf_adamw_clip_f32: %d partials for a norm range of %ld floats (tf_grad_sumsq_parts gives %d)", nparts,
+               (long)n_norm, sumsq_parts((long)n_norm));
+    TF_REQUIRE(max_norm > 0.f, "tf_adamw_clip_f32: max_norm must be positive (got %g)", (double)max_norm);
+    if (ls_state) TF_LAUNCH(grad_nonfinite_kernel, dim3(ew_blocks(n_norm / 4 + 1, 8192)), dim3(256), stream, g_norm, (long)(n_norm / 4), (long)n_norm, ls_state);
+    TF_LAUNCH(adamw_tick_kernel, dim3(1), dim3(64), stream, state_dev, (const float*)ls_state);
+    if (n > 0) TF_LAUNCH(adamw_kernel<ClipArgs>, dim3(ew_blocks(n / 4 + 1, 8192)), dim3(256), stream, p, g, m, v, (long)(n / 4), (long)n, (const float*)state_dev,
+                         beta1, beta2, eps, weight_decay, grad_scale, (const float*)ls_state, ClipArgs{partials, nparts, max_norm, norm_out});
+    if (ls_state) TF_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), stream, ls_state);
+    return launch_status("tf_adamw_clip_f32");
 }
 extern "C" int tf_lidar_hist_f32(const float* points, const int32_t* num_points, int B, int max_points, int point_stride, float* out, void* stream) {
     TF_REQUIRE(points && out && B > 0 && max_points >= 0 && point_stride >= 3, "tf_lidar_hist_f32: bad arguments");

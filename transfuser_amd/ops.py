@@ -1561,6 +1561,36 @@ def adamw_dynscale_(p, g, m, v, state, ls_state, g_check, beta1=0.9, beta2=0.999
     _hbm_end(_h, "adamw (28 B / parameter: p, g, m, v read; p, m, v written)", 28 * p.numel() + 4 * g_check.numel())
 
 
+def grad_sumsq_parts(n):
+    """Partial sums tf_grad_sumsq_f32 writes for a range of n floats: a function of n alone (never of the device)."""
+    return int(L().tf_grad_sumsq_parts(ctypes.c_int64(n)))
+
+
+def grad_sumsq(g, partials=None):
+    """Partial sums of squares of the flat fp32 range ``g`` -> ``partials`` (grad_sumsq_parts(g.numel()) floats; the caller's scratch when given).
+    One plain store per block, no atomics: their sum in index order is a fixed-order sum, bitwise reproducible."""
+    n = g.numel()
+    if partials is None:
+        partials = torch.empty(grad_sumsq_parts(n), dtype=torch.float32, device=g.device)
+    assert g.is_contiguous() and partials.numel() == grad_sumsq_parts(n), (n, partials.numel())
+    _h = _hbm_begin()
+    check(L().tf_grad_sumsq_f32(ptr(g), ctypes.c_int64(n), ptr(partials), stream_of(g)), "tf_grad_sumsq_f32")
+    _hbm_end(_h, "grad_sumsq (4 B / gradient read)", 4 * n)
+    return partials
+
+
+def adamw_clip_(p, g, m, v, state, g_norm, partials, max_norm, norm_out, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, ls_state=None):
+    """AdamW with the gradients clipped to the global norm ``max_norm`` (torch.nn.utils.clip_grad_norm_'s coefficient) on their way in.
+    ``partials`` = grad_sumsq(g_norm): the norm range may be wider than the update range ``g`` (a ZeRO-1 shard clips by the norm of the whole
+    arena).  ``norm_out`` (1 float) receives the pre-clip total norm of grad_scale * g_norm.  With ``ls_state`` the step runs under the dynamic
+    loss scale as adamw_dynscale_ does (overflow check over g_norm, gradients x grad_scale / scale, skip-or-update)."""
+    _h = _hbm_begin()
+    check(L().tf_adamw_clip_f32(ptr(p), ptr(g), ptr(m), ptr(v), ctypes.c_int64(p.numel()), ptr(state), ctypes.c_float(beta1), ctypes.c_float(beta2),
+                                ctypes.c_float(eps), ctypes.c_float(weight_decay), ctypes.c_float(grad_scale), ptr(g_norm), ctypes.c_int64(g_norm.numel()),
+                                ptr(partials), int(partials.numel()), ctypes.c_float(max_norm), ptr(norm_out), ptr(ls_state), stream_of(p)), "tf_adamw_clip_f32")
+    _hbm_end(_h, "adamw (28 B / parameter: p, g, m, v read; p, m, v written)", 28 * p.numel())
+
+
 def cast_bf16(x, out=None):
     """fp32 -> bf16 (round to nearest even)."""
     if out is None:

@@ -15,7 +15,9 @@ AdamW optimiser (:142) and the DDP gradient all-reduce (:134), re-designed for M
   rank the backward is cut at the fusion-stage boundaries into segments (one graph each) and the
   arena is laid out in backward-ready order, so the all-reduce of the ~130 M stage-4 / head gradients
   runs on the side stream while stages 3..1 are still being differentiated (DDP's overlap,
-  train.py:134, without hooks).
+  train.py:134, without hooks).  ``accumulate=k`` adds the gradients of k ``train_step`` calls before one
+  update (the effective batch of k ranks on one GPU), ``max_grad_norm`` clips the global gradient norm
+  inside the AdamW launch; both are off by default.
 """
 import os
 
@@ -156,10 +158,18 @@ class FlatAdamW:
 
     ``shard=(rank, world)`` = the reference's ``--zero_redundancy_optimizer 1`` (train.py:143-146, ZeRO stage 1): every rank keeps the
     AdamW moments of - and updates - only its contiguous 1/world slice of the arena; ``GradReducer.all_gather_params`` then circulates
-    the updated slices (what ZeroRedundancyOptimizer's parameter broadcast does).  Same parameter trajectory, 1/world of the state."""
+    the updated slices (what ZeroRedundancyOptimizer's parameter broadcast does).  Same parameter trajectory, 1/world of the state.
 
-    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, shard=None):
+    ``max_grad_norm`` = ``torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm)`` in front of the update, without a pass that rewrites the
+    gradients: one read of the active gradient arena leaves partial sums of squares in scratch allocated HERE, once (so a captured graph reuses
+    it), and the AdamW kernel scales the gradients by the clip coefficient on their way in.  A shard clips by the norm of the WHOLE arena.
+    ``grad_norm`` (device scalar, no host sync) holds the pre-clip norm of the gradients x ``grad_scale`` after every clipped step."""
+
+    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, shard=None, max_grad_norm=None):
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError("max_grad_norm must be positive (got %r); None = no clipping" % (max_grad_norm,))
         self.arena = arena
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         n = arena.active_numel
         self.lo, self.hi = 0, n
@@ -173,6 +183,10 @@ class FlatAdamW:
         self.exp_avg = torch.zeros(m, dtype=torch.float32, device=arena.params.device)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
         self.state = torch.tensor([0.0, lr], dtype=torch.float32, device=arena.params.device)  # {step, lr} on the device
+        self.grad_norm = None
+        if self.max_grad_norm is not None:
+            self._sumsq_parts = torch.empty(ops.grad_sumsq_parts(n), dtype=torch.float32, device=arena.params.device)
+            self.grad_norm = torch.zeros((), dtype=torch.float32, device=arena.params.device)
 
     def set_lr(self, lr):
         self.state[1] = lr   # train.py:194-199 (x0.1 at epochs 30 / 40)
@@ -183,14 +197,24 @@ class FlatAdamW:
     def step(self):
         a = self.arena
         ls = getattr(self, "ls_state", None)
-        if ls is not None:      # fp16 mode with the dynamic loss scale: overflow check over the WHOLE (reduced) gradient arena, skip-or-update, scale update
+        if ls is not None and self.max_grad_norm is None:      # fp16 mode with the dynamic loss scale: overflow check over the WHOLE (reduced) gradient arena, skip-or-update, scale update
             ops.adamw_dynscale_(a.params[self.lo:self.hi], a.grads[self.lo:self.hi], self.exp_avg, self.exp_avg_sq, self.state, ls, a.grads[:a.active_numel],
                                 self.betas[0], self.betas[1], self.eps, self.weight_decay)
             return
-        gs = getattr(self, "grad_scale", 1.0)
-        red = getattr(self, "reducer", None)
-        if red is not None:      # defer_scale: the arena holds the all-reduced SUM, the mean's 1 / world rides on the gradient scale (GradReducer.grad_scale)
-            gs = gs * red.grad_scale()
+        # gradient scale = 1 / loss scale x the deferred 1 / world x the accumulation window's 1 / k (under the dynamic loss scale the kernel
+        # divides by the device-side scale itself and the reducer has already applied 1 / world: only 1 / k is left)
+        gs = getattr(self, "accum_scale", 1.0)
+        if ls is None:
+            gs = getattr(self, "grad_scale", 1.0) * gs
+            red = getattr(self, "reducer", None)
+            if red is not None:      # defer_scale: the arena holds the all-reduced SUM, the mean's 1 / world rides on the gradient scale (GradReducer.grad_scale)
+                gs = gs * red.grad_scale()
+        if self.max_grad_norm is not None:
+            g_all = a.grads[:a.active_numel]
+            ops.grad_sumsq(g_all, self._sumsq_parts)
+            ops.adamw_clip_(a.params[self.lo:self.hi], a.grads[self.lo:self.hi], self.exp_avg, self.exp_avg_sq, self.state, g_all, self._sumsq_parts,
+                            self.max_grad_norm, self.grad_norm, self.betas[0], self.betas[1], self.eps, self.weight_decay, grad_scale=gs, ls_state=ls)
+            return
         ops.adamw_(a.params[self.lo:self.hi], a.grads[self.lo:self.hi], self.exp_avg, self.exp_avg_sq, self.state, self.betas[0], self.betas[1],
                    self.eps, self.weight_decay, grad_scale=gs)
 
@@ -389,7 +413,8 @@ class Engine:
     DEFAULT_CUTS = ((4, 1, 3), (4, 1, 2), (4, 1, 1), 3, (3, 0, 0), 2, 1)
 
     def __init__(self, model, config, lr=1e-4, use_graph=False, group=None, bucket_mb=64.0, wp_only=False, autotune=True, plan_file=None,
-                 zero_redundancy_optimizer=False, sync_batch_norm=False, cuts=None, precision=None, grad_dtype="fp32", loss_scale=None, deterministic=None):
+                 zero_redundancy_optimizer=False, sync_batch_norm=False, cuts=None, precision=None, grad_dtype="fp32", loss_scale=None, deterministic=None,
+                 accumulate=1, max_grad_norm=None):
         """``cuts``: points (cut_key: int c = after fusion stage c; (i, 0, 0) = between the stage-i trunks and GPT i; (i, 1, j) = inside GPT i
         in front of Block j) at which the backward is cut into separately enqueued (and separately captured) segments whose gradient
         ranges are all-reduced while the next segment runs.  None = DEFAULT_CUTS when there is more than one rank (and the backbone is a
@@ -405,7 +430,21 @@ class Engine:
         pure function of (inputs, parameters, dropout seed, GEMM plans): bitwise equal run to run, and across processes that load the same plan file
         with ``autotune=False`` (nothing is tuned under the flag).  The flag is read when a kernel is ISSUED, so it is fixed into a captured graph at
         capture time: flipping it afterwards changes eager calls only.  Other precisions (their stored-operand kernels are not audited) and more
-        than one rank (the all-reduce order is RCCL's) raise NotImplementedError."""
+        than one rank (the all-reduce order is RCCL's) raise NotImplementedError.
+        ``accumulate`` = k: ``train_step`` stays one micro-batch per call; the gradients of k consecutive calls add up in the arena (zeroed when a
+        window starts) and every k-th call ends the window with the all-reduce (DDP ``no_sync`` on the others), the clip, ONE AdamW update with
+        the gradients x 1 / k, and the weight-copy refresh: arithmetically what k data-parallel ranks compute (per-micro-batch BatchNorm
+        statistics, mean gradient).  Two differences from DDP: the BatchNorm running statistics are updated by every micro-batch in turn (DDP
+        saves rank 0's buffers only), and each micro-batch draws its dropout masks from the seed that advances per call (ranks seed
+        independently).  Under the fp16 dynamic loss scale the scale is constant inside a window and an overflow skips the window's update.
+        ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_`` of the (mean) gradients in front of AdamW (FlatAdamW); ``optimizer.grad_norm`` is
+        the pre-clip norm as a device scalar.  Both off by default: same launches, same captured graph, same bits."""
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError("accumulate must be an integer >= 1 (got %r)" % (accumulate,))
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError("max_grad_norm must be positive (got %r); None = no clipping" % (max_grad_norm,))
+        self.accumulate = int(accumulate)
+        self._micro = 0      # micro-batches of the current window already accumulated
         self.model = model
         self.config = config
         if deterministic is not None and (next(model.parameters()).is_cuda or ops._lib.is_test_backend()):
@@ -440,9 +479,13 @@ class Engine:
         self.reducer = GradReducer(self.arena, group, bucket_mb, grad_dtype)
         self.zero = bool(zero_redundancy_optimizer) and self.reducer.world > 1      # train.py:143-146
         rank = dist.get_rank(group) if self.zero else 0
-        self.optimizer = FlatAdamW(self.arena, lr=lr, shard=(rank, self.reducer.world) if self.zero else None)
+        dynamic_ls = loss_scale is None and ops.get_precision() == "fp16"
+        if max_grad_norm is None and dynamic_ls and self.accumulate > 1:
+            max_grad_norm = float("inf")      # tf_adamw_dynscale_f32 has no gradient scale next to the device-side one: the window's 1 / k rides on the clipping entry, which never clips here
+        self.optimizer = FlatAdamW(self.arena, lr=lr, shard=(rank, self.reducer.world) if self.zero else None, max_grad_norm=max_grad_norm)
+        self.optimizer.accum_scale = 1.0 / self.accumulate
         self.ls_state = None
-        if loss_scale is None and ops.get_precision() == "fp16":
+        if dynamic_ls:
             dev = self.arena.params.device
             self.ls_state = torch.tensor([65536.0, 0.0, 0.0, float(getattr(config, "loss_scale_growth_interval", 2000))], dtype=torch.float32, device=dev)
             self.optimizer.ls_state = self.ls_state
@@ -510,7 +553,8 @@ class Engine:
                 ops.lowp_refresh_weights()
 
     def _piece0_impl(self, data):
-        self.optimizer.zero_grad()
+        if self.accumulate == 1:      # a window of k > 1 micro-batches is zeroed once, by _begin_micro, outside the (captured) piece
+            self.optimizer.zero_grad()
         losses = self.load_data_compute_loss(data)
         keys = list(losses)                  # train.py:307-311: loss = sum of weight * detailed loss, in dictionary order - one launch per direction
         if ops._AB_WSUM and 1 <= len(keys) <= 16 and all(v.dim() == 0 and v.dtype == torch.float32 and v.is_contiguous() for v in losses.values()):
@@ -566,15 +610,36 @@ class Engine:
         if seed is not None:
             seed.add_(1)
 
+    def _begin_micro(self):
+        """Opens the next micro-batch of the accumulation window -> is it the window's last?  The first one zeroes the arena (for k > 1 an
+        eager memset on the step's stream, in front of the piece or its replay; with k == 1 piece 0 zeroes, inside the graph)."""
+        if self.accumulate > 1 and self._micro == 0:
+            self.arena.zero_grad()
+        self._micro = (self._micro + 1) % self.accumulate
+        return self._micro == 0
+
+    def grad_scale(self):
+        """The factor that turns the gradient arena (and every ``p.grad`` view of it) after a window's last ``train_step`` into the MEAN gradient
+        AdamW consumed, before clipping: 1 / accumulate x the reducer's deferred 1 / world x 1 / static loss scale (under the dynamic loss
+        scale the device-side scale of that step is a further divisor)."""
+        return self.optimizer.accum_scale * self.reducer.grad_scale() * (self.optimizer.grad_scale if self.ls_state is None else 1.0)
+
+    def discard_window(self):
+        """Drops a partial accumulation window (the end of an epoch, like ``drop_last``): the next call starts a new one."""
+        self._micro = 0
+
     def _eager_step(self, data):
-        out = self._fwd_bwd(data, reduce=True)
-        self._opt_step()
-        self._after_opt()
+        last = self._begin_micro()
+        out = self._fwd_bwd(data, reduce=last)      # DDP no_sync: only the window's last micro-batch all-reduces
+        if last:
+            self._opt_step()
+            self._after_opt()
         self._bump_seed()
         return out
 
     def train_step(self, data):
-        """Returns (total loss, dict of the 11 detailed losses) as device tensors (no host sync)."""
+        """One micro-batch: returns (total loss, dict of the 11 detailed losses) as device tensors (no host sync).  With ``accumulate`` = k
+        every k-th call also updates the parameters."""
         if not self.use_graph:
             return self._eager_step(data)
         if self._graphs is None:
@@ -583,10 +648,12 @@ class Engine:
             for k in self._static:
                 if self._static[k].data_ptr() != data[k].data_ptr():
                     self._static[k].copy_(data[k], non_blocking=True)
+        last = self._begin_micro()
         for i, g in enumerate(self._graphs):
             g.replay()
-            self.reducer.reduce_async(*self.arena.segment_ranges[i])      # no-op on a single rank
-        if self._opt_graph is not None:
+            if last:
+                self.reducer.reduce_async(*self.arena.segment_ranges[i])      # no-op on a single rank
+        if self._opt_graph is not None and last:
             self.reducer.finish()
             self._opt_graph.replay()
             self._after_opt()
@@ -605,7 +672,7 @@ class Engine:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):   # warm-up on a side stream (allocator + lazy inits) before capture
-            for _ in range(2):
+            for _ in range(2 if self.accumulate == 1 else self.accumulate):      # whole windows: the warm-up ends where a window starts
                 self._eager_step(self._static)
             with torch.no_grad():
                 for t, saved in snap:
@@ -615,7 +682,10 @@ class Engine:
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         del snap
-        fused_opt = self.reducer.world == 1 and self.n_pieces() == 1
+        # accumulate > 1: the piece graphs hold forward + backward + the seed bump and run for every micro-batch (no zeroing, no AdamW); the
+        # optimizer graph (gradient norm + AdamW + weight-copy refresh) is replayed by the window's last one only
+        window = self.accumulate > 1
+        fused_opt = self.reducer.world == 1 and self.n_pieces() == 1 and not window
         self._graphs = [torch.cuda.CUDAGraph() for _ in range(self.n_pieces())]
         # With a process group alive, c10d's watchdog THREAD polls the events of the (already finished) warm-up collectives; in the default
         # "global" capture mode such a query from another thread is an error that kills the process ("operation not permitted when stream is
@@ -626,17 +696,22 @@ class Engine:
             if fused_opt:
                 self._opt_step()
                 self._bump_seed()
+            elif window and self.n_pieces() == 1:
+                self._bump_seed()
         pool = self._graphs[0].pool()
         for i in range(1, self.n_pieces()):
             with torch.cuda.graph(self._graphs[i], pool=pool, **mode):
                 self._piece(i)
+                if window and i == self.n_pieces() - 1:
+                    self._bump_seed()
         if fused_opt:
             self._opt_graph = None
         else:
             self._opt_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._opt_graph, pool=pool, **mode):
                 self._opt_step()
-                self._bump_seed()
+                if not window:
+                    self._bump_seed()
 
     def save(self, path_prefix, epoch):
         """train.py:204-210,381-384: every rank calls it (the ZeRO state is consolidated collectively), rank 0 writes."""
@@ -706,7 +781,10 @@ class Trainer:
             for k, v in det.items():
                 detailed[k] += self.eng.detailed_weights[k] * v
             num_batches += 1
-        self.log_losses(float(loss_epoch), {k: float(v) for k, v in detailed.items()}, max(num_batches, 1), '')
+        self.eng.discard_window()      # --accumulate k: micro-batches left over when the loader ends are dropped, like drop_last (their gradients are never applied)
+        gn = self.eng.optimizer.grad_norm
+        extra = {} if gn is None else {"grad_norm": float(gn)}      # the epoch's last clipped step; the one host read of the device scalar
+        self.log_losses(float(loss_epoch), {k: float(v) for k, v in detailed.items()}, max(num_batches, 1), '', extra)
         self.cur_epoch += 1
 
     @torch.inference_mode()
@@ -724,7 +802,8 @@ class Trainer:
         self.log_losses(loss_epoch, detailed, max(num_batches, 1), 'val_')
         self.eng.model.train()
 
-    def log_losses(self, loss_epoch, detailed_losses_epoch, num_batches, prefix=''):
+    def log_losses(self, loss_epoch, detailed_losses_epoch, num_batches, prefix='', extra=None):
+        """``extra``: scalars of this rank logged as they are (not averaged over batches or ranks), e.g. grad_norm."""
         import json
         loss_epoch = loss_epoch / num_batches
         detailed = {k: v / num_batches for k, v in detailed_losses_epoch.items()}
@@ -738,6 +817,7 @@ class Trainer:
             rec = {prefix + "loss_total": sum(gathered_loss) / len(gathered_loss)}
             for k in detailed:
                 rec[prefix + k] = sum(g[k] for g in gathered_detailed) / self.world_size
+            rec.update({prefix + k: v for k, v in (extra or {}).items()})
             if self.writer is not None:
                 for k, v in rec.items():
                     self.writer.add_scalar(k, v, self.cur_epoch)
@@ -789,6 +869,8 @@ def build_parser():
     p.add_argument('--use_graph', type=int, default=1, help='capture the step into hipGraphs (falls back to eager where a flag requires it)')
     p.add_argument('--precision', type=str, default='fp32', choices=['fp32', 'f32x3', 'bf16'])
     p.add_argument('--deterministic', type=int, default=0, help='1: bitwise-reproducible fp32 train step on one GPU (fixed-order reductions instead of fp32 atomics; Engine(deterministic=True))')
+    p.add_argument('--accumulate', type=int, default=1, help='micro-batches per AdamW update: batch_size * accumulate on one GPU is the effective batch of that many data-parallel ranks (Engine(accumulate=k))')
+    p.add_argument('--max_grad_norm', type=float, default=0.0, help='clip the global gradient norm in front of AdamW (torch.nn.utils.clip_grad_norm_); 0 = off')
     p.add_argument('--height', type=int, default=160, help="RGB height of the synthetic samples (the dataset's crop is 160 x 704)")
     p.add_argument('--num_workers', type=int, default=None)
     p.add_argument('--width', type=int, default=704)
@@ -828,7 +910,8 @@ def main(argv=None):
         model.load_reference_checkpoint(args.load_file) if hasattr(model, "load_reference_checkpoint") else model.load_state_dict(torch.load(args.load_file, map_location=device))
     eng = Engine(model, config, lr=args.lr, use_graph=bool(args.use_graph) and cuda, wp_only=bool(args.wp_only),
                  zero_redundancy_optimizer=bool(args.zero_redundancy_optimizer), sync_batch_norm=bool(args.sync_batch_norm), precision=args.precision if cuda else None,
-                 deterministic=True if (args.deterministic and cuda) else None)
+                 deterministic=True if (args.deterministic and cuda) else None, accumulate=args.accumulate,
+                 max_grad_norm=args.max_grad_norm if args.max_grad_norm != 0 else None)
     if args.load_file is not None and os.path.exists(args.load_file.replace("model_", "optimizer_")):
         eng.optimizer.load_state_dict(torch.load(args.load_file.replace("model_", "optimizer_"), map_location=device))
     shared_dict = None
