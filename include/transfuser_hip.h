@@ -372,6 +372,13 @@ int tf_bn_fwd_f32(const float* x, int rows, int C, const float* gamma, const flo
 int tf_bn_zacc_floats(int C);
 int tf_bn_bwd_f32(const float* dz, const float* z, const float* x, int rows, int C, const float* gamma, const float* save_mean, const float* save_invstd,
                   float* dx, float* dres, float* dgamma, float* dbeta, float* ws, float* zacc, void* stream);
+/* BatchNorm2d backward of a layer that normalised with FROZEN statistics (the module in eval() inside a training step: F.batch_norm(x, running_mean,
+ * running_var, gamma, beta, training=False)); mean / invstd = what tf_bn_fwd_f32(training = 0) leaves in save_mean / save_invstd (running_mean,
+ * 1 / sqrt(running_var + eps)).  With g = dz [z > 0] (z NULL: no ReLU): dx = g gamma invstd, dres = g (optional), dgamma += sum g (x - mean) invstd,
+ * dbeta += sum g.  dgamma and dbeta are given together (then x, mean and ws = tf_workspace_bytes() are needed) or both NULL (frozen affine: one
+ * element-wise pass, x is not read).  The column sums are chunk partials + a finalize launch in every mode: no float atomics. */
+int tf_bn_bwd_frozen_f32(const float* dz, const float* z, const float* x, int rows, int C, const float* gamma, const float* mean, const float* invstd,
+                         float* dx, float* dres, float* dgamma, float* dbeta, float* ws, void* stream);
 /* out[seg][c] (+)= scale * sum_rows x (* [mask > 0]): SE squeeze / global average pool
  * (transfuser.py:203-205), bias gradients, pos_emb gradient. */
 int tf_colsum_f32(const float* x, const float* mask, int nseg, int rows_per_seg, int C, float scale, float* out, int accumulate, float* ws, void* stream);
@@ -513,6 +520,21 @@ int tf_grad_sumsq_f32(const float* g, int64_t n, float* partials, void* stream);
 int tf_adamw_clip_f32(float* p, const float* g, float* m, float* v, int64_t n, float* state_dev, float beta1, float beta2, float eps, float weight_decay,
                       float grad_scale, const float* g_norm, int64_t n_norm, const float* partials, int nparts, float max_norm, float* norm_out,
                       float* ls_state, void* stream);
+/* AdamW parameter groups (torch.optim.AdamW's param_groups; extends train.py:142, which has one group).  The range is whole tiles of 64 floats
+ * (n % 64 == 0, n >= 64); tile_group[t] (n / 64 bytes) names the group of floats [64 t, 64 t + 64) and table = [ngroups][{lr_mult, weight_decay,
+ * frozen}] floats, both on the device, ngroups in 1..255 (an id >= ngroups reads the last row).  A group updates with lr = state_dev[1] * lr_mult
+ * and its own decoupled weight decay; frozen != 0 skips the tile before any load: p, m, v are neither read nor written, g is not read.  Values
+ * written to the table between two replays of a captured graph take effect without a recapture.  For a ZeRO-1 shard [lo, hi) pass
+ * tile_group + lo / 64 with the shard's p / g / m / v.
+ * tf_grad_sumsq_groups_f32 = tf_grad_sumsq_f32 without the frozen tiles (clip_grad_norm_ only sees parameters that have a gradient): the same
+ * P = tf_grad_sumsq_parts(n) plain-store partials, no atomics, legal under tf_set_deterministic(1).
+ * tf_adamw_groups_f32 = tf_adamw_scaled_f32 per group; with partials != NULL it clips like tf_adamw_clip_f32 (nparts = tf_grad_sumsq_parts(n_norm)
+ * partials of the norm range, max_norm > 0, pre-clip norm to norm_out[0]); partials NULL: no clipping, nparts / n_norm / max_norm / norm_out
+ * unused.  There is no dynamic-loss-scale form. */
+int tf_grad_sumsq_groups_f32(const float* g, int64_t n, const uint8_t* tile_group, const float* table, int ngroups, float* partials, void* stream);
+int tf_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, float* state_dev, float beta1, float beta2, float eps, float grad_scale,
+                        const uint8_t* tile_group, const float* table, int ngroups, const float* partials, int nparts, int64_t n_norm, float max_norm,
+                        float* norm_out, void* stream);
 /* lidar_to_histogram_features (data.py:446-470): points (B, max_points, stride>=3) f32 -> (B,2,256,256),
  * integer-exact; num_points may be NULL. */
 int tf_lidar_hist_f32(const float* points, const int32_t* num_points, int B, int max_points, int point_stride, float* out, void* stream);

@@ -166,6 +166,79 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// ---- AdamW parameter groups (torch.optim.AdamW's param_groups; the reference's train.py:142 has one group).  Membership is kept per arena TILE of
+// kTileFloats floats (train.py's _ALIGN: the arena starts a new tile wherever two neighbours belong to different groups, so no tile straddles two):
+// tile_group[t] = the group of floats [64 t, 64 t + 64), table = [ngroups][{lr_mult, weight_decay, frozen}] floats on the device - values written
+// there between two replays of a captured graph take effect without a recapture, like state[1].  A frozen tile is skipped before any load: p, m, v
+// are neither read nor written and its gradients never reach the norm.  The two kernels below are separate from adamw_kernel<> / grad_sumsq_kernel
+// (whose code stays what it is); with lr_mult = 1 the per-element expression sequence is the plain kernel's, so one default group gives its bits.
+constexpr int kTileFloats = 64, kTileVec4 = kTileFloats / 4, kGroupRow = 3;
+constexpr int kGroupGridCap = 2048;      // 8 resident blocks of 256 threads per CU x 256 CUs: past 2048 x 1024 floats a block makes further grid-stride trips
+__device__ __forceinline__ const float* group_row(const uint8_t* __restrict__ tile_group, const float* __restrict__ table, int ngroups, long vec4) {
+    const int id = tile_group[vec4 / kTileVec4];
+    return table + kGroupRow * (id < ngroups ? id : ngroups - 1);      // an id past the table reads the last row, never past the allocation
+}
+__global__ void __launch_bounds__(256) grad_sumsq_groups_kernel(const float* __restrict__ g, long n4, const uint8_t* __restrict__ tile_group,
+                                                                const float* __restrict__ table, int ngroups, float* __restrict__ partials) {
+    __shared__ float red[4];
+    const long stride = (long)gridDim.x * 256;
+    float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;          // grad_sumsq_kernel's accumulators and its order of additions (trip by trip)
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += 4 * stride) {
+        float4 a[4];
+        bool live[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                      // four 16-byte loads in flight from clamped indices, independent of the id -> table chain beside
+            const long j = i + u * stride, jj = j < n4 ? j : i;      // them: the selection is applied to the VALUES (a frozen tile's NaN is dropped, not multiplied)
+            a[u] = reinterpret_cast<const float4*>(g)[jj];
+            live[u] = j < n4 && group_row(tile_group, table, ngroups, jj)[2] == 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (live[u]) { sx += a[u].x * a[u].x; sy += a[u].y * a[u].y; sz += a[u].z * a[u].z; sw += a[u].w * a[u].w; }
+    }
+    const float t = block_sum<4>((sx + sy) + (sz + sw), red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+template <class... CLIP>
+__global__ void __launch_bounds__(256) adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                           long n4, const float* __restrict__ state, float b1, float b2, float eps, float gs,
+                                                           const uint8_t* __restrict__ tile_group, const float* __restrict__ table, int ngroups, CLIP... clip) {
+    if constexpr (sizeof...(CLIP) > 0) {      // the prologue of adamw_kernel<ClipArgs>: every block re-reduces the partials in one fixed order
+        __shared__ float red[4];
+        const ClipArgs c = (clip, ...);
+        float s = 0.f;
+        for (int i = threadIdx.x; i < c.nparts; i += 256) s += c.partials[i];
+        s = block_sum<4>(s, red);
+        const float norm = gs * sqrtf(s);
+        const float r = c.max_norm / (norm + 1e-6f);
+        gs *= r > 1.f ? 1.f : r;
+        if (blockIdx.x == 0 && threadIdx.x == 0) c.norm_out[0] = norm;
+    }
+    const float step = state[0], lr = state[1];
+    const float bc1 = 1.f - powf(b1, step), bc2 = 1.f - powf(b2, step);
+    const float inv_sq_bc2 = 1.f / sqrtf(bc2);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float* row = group_row(tile_group, table, ngroups, i);
+        if (row[2] != 0.f) continue;                       // frozen: nothing of this tile is touched
+        const float lr_g = lr * row[0];
+        const float step_size = lr_g / bc1, decay = 1.f - lr_g * row[1];
+        float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            G[k] *= gs;
+            P[k] *= decay;
+            M[k] = b1 * M[k] + (1.f - b1) * G[k];
+            V[k] = b2 * V[k] + (1.f - b2) * G[k] * G[k];
+            P[k] -= step_size * (M[k] / (sqrtf(V[k]) * inv_sq_bc2 + eps));
+        }
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+    }
+}
+
 // LiDAR -> 2-bin BEV histogram (data.py:446-470), integer-exact:
 //   valid iff -16 <= x <= 16 and -32 <= y <= 0; xbin = min(floor(8x) + 128, 255), ybin = min(floor(8y) + 256, 255)
 //   channel = (z <= -2.3) ? 1 : 0;  out[c][ybin][255 - xbin] = min(count, 5) / 5
@@ -370,6 +443,42 @@ extern "C" int tf_adamw_clip_f32(float* p, const float* g, float* m, float* v, i
                          beta1, beta2, eps, weight_decay, grad_scale, (const float*)ls_state, ClipArgs{partials, nparts, max_norm, norm_out});
     if (ls_state) TF_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), stream, ls_state);
     return launch_status("tf_adamw_clip_f32");
+}
+// ---- parameter groups (include/transfuser_hip.h): the arguments the two entries share are checked in one place
+namespace {
+inline int groups_args_ok(const char* who, int64_t n, const uint8_t* tile_group, const float* table, int ngroups) {
+    TF_REQUIRE(n >= kTileFloats && n % kTileFloats == 0, "%s: the range must be whole %d-float tiles (got %ld floats)", who, kTileFloats, (long)n);
+    TF_REQUIRE(tile_group && table, "%s: tile_group and the group table must not be NULL", who);
+    TF_REQUIRE(ngroups >= 1 && ngroups <= 255, "%s: 1..255 groups (got %d)", who, ngroups);
+    return 0;
+}
+}  // namespace
+extern "C" int tf_grad_sumsq_groups_f32(const float* g, int64_t n, const uint8_t* tile_group, const float* table, int ngroups, float* partials, void* stream) {
+    TF_REQUIRE(g && partials, "tf_grad_sumsq_groups_f32: bad arguments");
+    TF_REQUIRE(aligned16(g), "tf_grad_sumsq_groups_f32: the range must be 16-byte aligned");
+    if (const int rc = groups_args_ok("tf_grad_sumsq_groups_f32", n, tile_group, table, ngroups)) return rc;
+    TF_LAUNCH(grad_sumsq_groups_kernel, dim3(sumsq_parts((long)n)), dim3(256), stream, g, (long)(n / 4), tile_group, table, ngroups, partials);
+    return launch_status("tf_grad_sumsq_groups_f32");
+}
+extern "C" int tf_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, float* state_dev, float beta1, float beta2, float eps,
+                                   float grad_scale, const uint8_t* tile_group, const float* table, int ngroups, const float* partials, int nparts,
+                                   int64_t n_norm, float max_norm, float* norm_out, void* stream) {
+    TF_REQUIRE(p && g && m && v && state_dev, "tf_adamw_groups_f32: bad arguments");
+    TF_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "tf_adamw_groups_f32: arenas must be 16-byte aligned");
+    if (const int rc = groups_args_ok("tf_adamw_groups_f32", n, tile_group, table, ngroups)) return rc;
+    if (partials) {
+        TF_REQUIRE(norm_out && n_norm >= 1, "tf_adamw_groups_f32: clipping needs norm_out and the norm range's size");
+        TF_REQUIRE(nparts == sumsq_parts((long)n_norm), "tf_adamw_groups_f32: %d partials for a norm range of %ld floats (tf_grad_sumsq_parts gives %d)", nparts,
+                   (long)n_norm, sumsq_parts((long)n_norm));
+        TF_REQUIRE(max_norm > 0.f, "tf_adamw_groups_f32: max_norm must be positive (got %g)", (double)max_norm);
+    }
+    const dim3 grid(ew_blocks(n / 4, kGroupGridCap));
+    TF_LAUNCH(adamw_tick_kernel, dim3(1), dim3(64), stream, state_dev, (const float*)nullptr);
+    if (partials) TF_LAUNCH(adamw_groups_kernel<ClipArgs>, grid, dim3(256), stream, p, g, m, v, (long)(n / 4), (const float*)state_dev, beta1, beta2, eps, grad_scale,
+                            tile_group, table, ngroups, ClipArgs{partials, nparts, max_norm, norm_out});
+    else TF_LAUNCH(adamw_groups_kernel<>, grid, dim3(256), stream, p, g, m, v, (long)(n / 4), (const float*)state_dev, beta1, beta2, eps, grad_scale, tile_group,
+                   table, ngroups);
+    return launch_status("tf_adamw_groups_f32");
 }
 extern "C" int tf_lidar_hist_f32(const float* points, const int32_t* num_points, int B, int max_points, int point_stride, float* out, void* stream) {
     TF_REQUIRE(points && out && B > 0 && max_points >= 0 && point_stride >= 3, "tf_lidar_hist_f32: bad arguments");

@@ -187,6 +187,18 @@ template <class G> struct BnBwdF {  // (g, g * xhat)
     }
 };
 
+// BatchNorm backward with FROZEN statistics (the module is in eval(): mean / invstd are constants, not functions of x): (g xhat, g) - LnDwF's order,
+// so ln_dw_finalize_kernel finishes the two column sums into dgamma / dbeta
+struct BnFrozenF {
+    GradZ grad; const float* x; const float* mean; const float* invstd; int C;
+    template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
+        const long e = row * C + c;
+        const vecf<V> a = ldv<V>(x + e), m = ldv<V>(mean + c), s = ldv<V>(invstd + c), g = grad.at(e, (int)row, c, a);
+#pragma unroll
+        for (int i = 0; i < V; ++i) { o[0].v[i] = g.v[i] * ((a.v[i] - m.v[i]) * s.v[i]); o[1].v[i] = g.v[i]; }
+    }
+};
+
 struct LnDwF {  // (dy * xhat, dy): the LayerNorm weight / bias gradient terms of one row; mean / rstd are per ROW
     const float* dy; const float* x; const float* mean; const float* rstd; int C;
     template <int V> __device__ __forceinline__ void eval(long row, int c, vecf<V>* o) const {
@@ -440,12 +452,15 @@ __global__ void __launch_bounds__(256) bn_fwd_finalize_parts_kernel(const float*
     }
 }
 __global__ void bn_eval_coef_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ rmean,
-                                    const float* __restrict__ rvar, float* __restrict__ coef, int C, float eps) {
+                                    const float* __restrict__ rvar, float* __restrict__ coef, int C, float eps, float* __restrict__ save_mean,
+                                    float* __restrict__ save_invstd) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     const float sc = gamma[c] / sqrtf(rvar[c] + eps);
     coef[c] = sc;
     coef[C + c] = beta[c] - rmean[c] * sc;
+    if (save_mean) save_mean[c] = rmean[c];                             // what the frozen-statistics backward normalises with (tf_bn_bwd_frozen_f32)
+    if (save_invstd) save_invstd[c] = 1.f / sqrtf(rvar[c] + eps);
 }
 // dgamma += sum g*xhat, dbeta += sum g; dx = A*g + Bc*x + Cc  (coef = [A | Bc | Cc])
 __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __restrict__ ws, const float* __restrict__ gamma, const float* __restrict__ mean,
@@ -532,6 +547,16 @@ template <class G> struct BnBwdApplyF {   // g from the source G (-> dres when n
         if (dres) stv<V>(dres + o, g);
         r = bn_bwd_dx(g, a, A, Bc, Cc);
         if (dx) stv<V>(dx + o, r);
+    }
+};
+struct BnFrozenApplyF {   // g = dz [z > 0] (-> dres when not NULL), dx = g * (gamma invstd): no term through the statistics, x is not read
+    GradZ grad; const float* gamma; const float* invstd; float* dx; float* dres; int C;
+    template <int V> __device__ __forceinline__ void operator()(long o, int row, int c, vecf<V>& r) const {
+        const vecf<V> ga = ldv<V>(gamma + c), s = ldv<V>(invstd + c), g = grad.at(o, row, c, ga);
+        if (dres) stv<V>(dres + o, g);
+#pragma unroll
+        for (int i = 0; i < V; ++i) r.v[i] = g.v[i] * (ga.v[i] * s.v[i]);
+        stv<V>(dx + o, r);
     }
 };
 // ---- single-pass-after-reduce BatchNorm: the statistics were ACCUMULATED with atomics into acc = [S1 | S2] (2*C floats), so there is
@@ -793,7 +818,7 @@ extern "C" int tf_bn_fwd_f32(const float* x, int rows, int C, const float* gamma
     } else {
         TF_REQUIRE(running_mean && running_var, "tf_bn_fwd_f32: eval needs running statistics");
         TF_LAUNCH(bn_eval_coef_kernel, dim3(cdiv(C, 256)), dim3(256), stream, gamma, beta, (const float*)running_mean, (const float*)running_var,
-                  coef, C, eps);
+                  coef, C, eps, save_mean, save_invstd);
     }
     launch_bn_apply(x, coef, res, relu, y, rows, C, stream);
     return launch_status("tf_bn_fwd_f32");
@@ -834,6 +859,25 @@ extern "C" int tf_bn_bwd_f32(const float* dz, const float* z, const float* x, in
     const bool v4 = (C % 4 == 0) && aligned16(dz) && aligned16(x) && aligned16(dx) && (!z || aligned16(z)) && (!dres || aligned16(dres));
     launch_ew(BnBwdApplyF<GradZ>{grad, x, coef, dx, dres, C}, v4, (long)rows * C, stream);
     return launch_status("tf_bn_bwd_f32");
+}
+
+// BatchNorm2d backward with frozen statistics (include/transfuser_hip.h): the layer normalised with its running statistics (eval mode inside a
+// training step), so dx = g gamma invstd with g = dz [z > 0].  dgamma / dbeta (both or neither; ACCUMULATED) take the fixed-order chunk partials +
+// finalize form in every mode - no float atomics; without them (frozen affine) the call is the element-wise pass alone.
+extern "C" int tf_bn_bwd_frozen_f32(const float* dz, const float* z, const float* x, int rows, int C, const float* gamma, const float* mean,
+                                    const float* invstd, float* dx, float* dres, float* dgamma, float* dbeta, float* ws, void* stream) {
+    TF_REQUIRE(dz && gamma && invstd && dx && rows > 0 && C > 0, "tf_bn_bwd_frozen_f32: bad arguments");
+    TF_REQUIRE((dgamma != nullptr) == (dbeta != nullptr), "tf_bn_bwd_frozen_f32: dgamma and dbeta are given together or not at all");
+    TF_REQUIRE(!dgamma || (x && mean && ws), "tf_bn_bwd_frozen_f32: the parameter gradients need x, mean and the workspace");
+    const GradZ grad{dz, z};
+    const bool v4 = (C % 4 == 0) && aligned16(dz) && aligned16(dx) && (!z || aligned16(z)) && (!dres || aligned16(dres)) && aligned16(gamma) && aligned16(invstd);
+    if (dgamma) {
+        const RedPlan p = plan_reduce(rows, C, 1, 2, v4 && aligned16(x) && aligned16(mean));
+        launch_reduce<2>(p, BnFrozenF{grad, x, mean, invstd, C}, rows, C, 1, ws, stream);
+        TF_LAUNCH(ln_dw_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), stream, (const float*)ws, dgamma, dbeta, C, p.nchunks);
+    }
+    launch_ew(BnFrozenApplyF{grad, gamma, invstd, dx, dres, C}, v4, (long)rows * C, stream);
+    return launch_status("tf_bn_bwd_frozen_f32");
 }
 
 // out[seg][c] (+)= scale * sum over the segment's rows of x (* [mask > 0]).  Uses: SE squeeze /

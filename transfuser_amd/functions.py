@@ -100,12 +100,21 @@ def _bn(x, bn, res=None, relu=False, stat=None):
         y, sm, si = ops.bn_fwd_parts(x, stat, bn.weight, bn.bias, bn.running_mean, bn.running_var, res, relu, bn.momentum, bn.eps)
         return y, (sm, si)
     y, sm, si = ops.bn_fwd(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, res, relu, bn.training, bn.momentum, bn.eps)
-    return y, (sm, si)
+    return y, (sm, si) if bn.training else _FrozenStats((sm, si))
+
+
+class _FrozenStats(tuple):
+    """(running_mean, 1 / sqrt(running_var + eps)) of a BatchNorm that ran in eval mode: its backward has no term through the statistics."""
 
 
 def _bn_bwd(dz, z, x, bn, st, want_dres=False):
+    """Backward of ``_bn``.  Every BatchNorm of the block Functions that is in eval() during a training step (frozen-BN fine-tuning) ends up HERE
+    with ``_FrozenStats``: the folded / 16-bit forms (bn_bwd_remask*, bn_bwd16) are only reachable from forwards gated on ``bn.training``."""
     if len(st) == 4:
         return _bn_sync_bwd(dz, z, x, bn, st, want_dres)
+    if isinstance(st, _FrozenStats):
+        affine = bn.weight.requires_grad or bn.bias.requires_grad      # a frozen affine pair needs no column sums: one element-wise pass
+        return ops.bn_bwd(dz, z, x, bn.weight, st[0], st[1], gbuf(bn.weight) if affine else None, gbuf(bn.bias) if affine else None, want_dres, frozen=True)
     return ops.bn_bwd(dz, z, x, bn.weight, st[0], st[1], gbuf(bn.weight), gbuf(bn.bias), want_dres)
 
 

@@ -1057,7 +1057,8 @@ def zero_scratch(n, device):
 
 
 def bn_fwd(x, gamma, beta, rmean, rvar, res=None, relu=False, training=True, momentum=0.1, eps=1e-5):
-    """x: (..., C) NHWC; returns (y, save_mean, save_invstd)."""
+    """x: (..., C) NHWC; returns (y, save_mean, save_invstd): the batch statistics when training, else running_mean and 1 / sqrt(running_var + eps)
+    (what bn_bwd(frozen=True) takes)."""
     C = x.shape[-1]
     rows = x.numel() // C
     y = torch.empty_like(x)
@@ -1232,11 +1233,21 @@ def bn_bwd_remask_se(dy, gate, dmean, x, coef, gamma, sm, si, dgamma, dbeta):
     return dx
 
 
-def bn_bwd(dz, z, x, gamma, sm, si, dgamma, dbeta, want_dres=False):
+def bn_bwd(dz, z, x, gamma, sm, si, dgamma, dbeta, want_dres=False, frozen=False):
+    """BatchNorm backward -> (dx, dres); dgamma / dbeta are accumulated.  ``frozen``: the forward normalised with the running statistics
+    (bn_fwd(training=False), whose save_mean / save_invstd are sm / si): dx = g gamma invstd, no term through the statistics
+    (tf_bn_bwd_frozen_f32); dgamma = dbeta = None then skips the column sums (frozen affine)."""
     C = x.shape[-1]
     rows = x.numel() // C
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
+    if frozen:
+        assert (dgamma is None) == (dbeta is None)
+        _h = _hbm_begin()
+        check(L().tf_bn_bwd_frozen_f32(ptr(_c(dz)), ptr(z), ptr(_c(x)), rows, C, ptr(gamma), ptr(sm), ptr(si), ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta),
+                                       ptr(workspace(x.device)), stream_of(x)), "tf_bn_bwd_frozen_f32")
+        _hbm_end(_h, "batchnorm backward, frozen statistics", 4 * x.numel() * ((1 + (z is not None)) * (1 + (dgamma is not None)) + (dgamma is not None) + 1 + (dres is not None)))
+        return dx, dres
     zacc = zero_scratch(32 * C, x.device) if not _DBG_LEGACY_BNB else None
     _h = _hbm_begin()
     check(L().tf_bn_bwd_f32(ptr(_c(dz)), ptr(z), ptr(_c(x)), rows, C, ptr(gamma), ptr(sm), ptr(si), ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta),
@@ -1589,6 +1600,39 @@ def adamw_clip_(p, g, m, v, state, g_norm, partials, max_norm, norm_out, beta1=0
                                 ctypes.c_float(eps), ctypes.c_float(weight_decay), ctypes.c_float(grad_scale), ptr(g_norm), ctypes.c_int64(g_norm.numel()),
                                 ptr(partials), int(partials.numel()), ctypes.c_float(max_norm), ptr(norm_out), ptr(ls_state), stream_of(p)), "tf_adamw_clip_f32")
     _hbm_end(_h, "adamw (28 B / parameter: p, g, m, v read; p, m, v written)", 28 * p.numel())
+
+
+GROUP_TILE = 64      # floats per arena tile of the parameter-group kernels (train._ALIGN)
+
+
+def grad_sumsq_groups(g, tile_group, table, partials=None):
+    """grad_sumsq without the tiles of frozen groups: ``tile_group`` (uint8, one id per 64 floats of ``g``), ``table`` (ngroups, 3) =
+    [lr_mult, weight_decay, frozen] on the device.  A frozen tile's gradients are dropped by selection (a NaN there never reaches the norm)."""
+    n = g.numel()
+    if partials is None:
+        partials = torch.empty(grad_sumsq_parts(n), dtype=torch.float32, device=g.device)
+    assert g.is_contiguous() and partials.numel() == grad_sumsq_parts(n), (n, partials.numel())
+    assert tile_group.dtype == torch.uint8 and tile_group.is_contiguous() and tile_group.numel() * GROUP_TILE >= n and table.is_contiguous(), (n, tile_group.shape)
+    _h = _hbm_begin()
+    check(L().tf_grad_sumsq_groups_f32(ptr(g), ctypes.c_int64(n), ptr(tile_group), ptr(table), int(table.numel() // 3), ptr(partials), stream_of(g)),
+          "tf_grad_sumsq_groups_f32")
+    _hbm_end(_h, "grad_sumsq (4 B / gradient read)", 4 * n)
+    return partials
+
+
+def adamw_groups_(p, g, m, v, state, tile_group, table, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, partials=None, n_norm=0, max_norm=0.0, norm_out=None):
+    """AdamW with parameter groups at tile granularity (tf_adamw_groups_f32): a tile of group i updates with lr x table[i, 0] and weight decay
+    table[i, 1]; table[i, 2] != 0 freezes it (p, m, v untouched, g unread).  ``tile_group`` starts at the tile of p[0] (a ZeRO-1 shard passes
+    the arena's table offset by lo / 64).  ``partials`` = grad_sumsq_groups over the norm range of ``n_norm`` floats: clip to ``max_norm`` as
+    adamw_clip_ does, pre-clip norm to ``norm_out``."""
+    n = p.numel()
+    assert tile_group.dtype == torch.uint8 and tile_group.is_contiguous() and tile_group.numel() * GROUP_TILE >= n and table.is_contiguous(), (n, tile_group.shape)
+    _h = _hbm_begin()
+    check(L().tf_adamw_groups_f32(ptr(p), ptr(g), ptr(m), ptr(v), ctypes.c_int64(n), ptr(state), ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps),
+                                  ctypes.c_float(grad_scale), ptr(tile_group), ptr(table), int(table.numel() // 3), ptr(partials),
+                                  int(partials.numel()) if partials is not None else 0, ctypes.c_int64(n_norm), ctypes.c_float(max_norm), ptr(norm_out), stream_of(p)),
+          "tf_adamw_groups_f32")
+    _hbm_end(_h, "adamw (28 B / parameter: p, g, m, v read; p, m, v written)", 28 * n)
 
 
 def cast_bf16(x, out=None):

@@ -108,6 +108,10 @@ class PointPillarNet(nn.Module):
         """(B, nx, ny, C + Ce) NHWC: already rotated (model.py:738) and with ``extra`` (B, Ce, nx, ny) appended (model.py:742)."""
         pts = lidar_list if torch.is_tensor(lidar_list) else torch.stack(list(lidar_list))
         assert pts.dim() == 3 and pts.shape[2] == 4 and pts.dtype == torch.float32, "lidar_raw must be (B, N, 4) float32"
+        if (torch.is_grad_enabled() and (pts.requires_grad or any(p.requires_grad for p in self.parameters()))
+                and any(isinstance(m, nn.modules.batchnorm._BatchNorm) and not m.training for m in self.point_net.net)):
+            raise NotImplementedError("PointPillars BatchNorm1d in eval() under gradients: the point net's backward has the batch-statistics form only "
+                                      "(frozen statistics are not implemented here) - keep the point net in train(), or freeze all of it")
         return PillarFn.apply(pts.contiguous(), num_points.to(torch.int32), extra, self, *self.parameters())
 
     def forward(self, lidar_list, num_points):

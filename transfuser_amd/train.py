@@ -17,7 +17,9 @@ AdamW optimiser (:142) and the DDP gradient all-reduce (:134), re-designed for M
   runs on the side stream while stages 3..1 are still being differentiated (DDP's overlap,
   train.py:134, without hooks).  ``accumulate=k`` adds the gradients of k ``train_step`` calls before one
   update (the effective batch of k ranks on one GPU), ``max_grad_norm`` clips the global gradient norm
-  inside the AdamW launch; both are off by default.
+  inside the AdamW launch; both are off by default.  Fine-tuning: ``freeze`` / ``requires_grad = False`` parameters are filed behind the
+  arena's active range (never updated, decayed or counted in the norm), their BatchNorms stay in eval(), and ``param_groups`` give name
+  prefixes their own learning-rate multiplier and weight decay (FlatAdamW ``groups``, one id per 64-float arena tile); off by default.
 """
 import os
 
@@ -90,10 +92,17 @@ def cut_key(c):
 
 
 class ParamArena:
-    def __init__(self, model, cuts=()):
+    def __init__(self, model, cuts=(), group_of=None):
         """``cuts`` = points at which the backward is cut (cut_key: ints = after fusion stage c, tuples = the backbone's finer cut points,
         e.g. (4, 1, 2) = inside GPT-4 in front of Block 2): parameters are then grouped by backward segment, first-finished segment first, and
-        ``segment_ranges`` lists each segment's [lo, hi) float range of the arena."""
+        ``segment_ranges`` lists each segment's [lo, hi) float range of the arena.
+        Parameters with ``requires_grad == False`` (FROZEN) are filed with the never-reached ones behind ``active_numel``: the norm, the optimizer,
+        the overflow check, the all-reduce and a ZeRO-1 shard all work on [0, active_numel) and so never see them, in every mode.
+        ``group_of`` = {parameter name: optimizer group id < 256} (FlatAdamW ``groups``): ``tile_group`` then holds one uint8 id per _ALIGN-float
+        tile.  Every parameter already starts on a tile except inside the adjacency sets of ``_group_key`` (K/Q/V of an attention layer, the eight
+        merged head convolutions); those stay back-to-back only among members of ONE group and of one frozen state - a set split across groups is
+        laid out as several aligned runs, and ``attn.fused()`` / ``model.merged_head_convs`` fall back by their own adjacency checks.  Without
+        ``group_of`` and with nothing frozen the layout, ``segment_ranges`` and ``active_numel`` are what they were without these arguments."""
         named, seen = [], set()
         for n, p in model.named_parameters(remove_duplicate=True):
             if id(p) not in seen:
@@ -102,6 +111,9 @@ class ParamArena:
         # parameters the reference's autograd graph never reaches keep grad None there and torch.optim.AdamW skips them
         # (no weight decay either): they go to the END of the arena, outside the range the optimizer updates.
         unused = {id(p) for m in model.modules() if hasattr(m, "unused_parameters") for p in m.unused_parameters()}
+        self.frozen = [n for n, p in named if not p.requires_grad]      # torch.optim.AdamW / clip_grad_norm_ skip them as well: same place
+        unused |= {id(p) for _, p in named if not p.requires_grad}
+        gid = (lambda n: int(group_of[n])) if group_of else (lambda n: 0)
         named = [t for t in named if id(t[1]) not in unused] + [t for t in named if id(t[1]) in unused]
         cuts = sorted(set(cut_key(c) for c in cuts), reverse=True)
         seg_of = lambda name: sum(1 for c in cuts if param_key(name) <= c)       # 0 = produced first in the backward
@@ -111,6 +123,7 @@ class ParamArena:
         groups, order = {}, []
         for n, p in named:
             k, rank = _group_key(n)
+            k = (k, id(p) in unused, gid(n))      # an adjacency set never mixes live / inactive members or optimizer groups: each run starts on a tile
             if k not in groups:
                 groups[k] = []
                 order.append(k)
@@ -128,6 +141,12 @@ class ParamArena:
         self.params = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         self.grads = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         self.layout = layout
+        self.tile_group = None
+        if group_of:
+            tiles = torch.zeros(self.numel // _ALIGN, dtype=torch.uint8)      # padding tiles: group 0 (all-zero p, g, m, v stay zero under any group)
+            for n, p, o in layout:
+                tiles[o // _ALIGN:(o + p.numel() + _ALIGN - 1) // _ALIGN] = gid(n)
+            self.tile_group = tiles.to(dev)
         self.n_params = sum(p.numel() for _, p in named)
         # [lo, hi) of every backward segment (aligned; together they cover [0, active_numel)); one range when there are no cuts
         nseg = len(cuts) + 1
@@ -163,11 +182,28 @@ class FlatAdamW:
     ``max_grad_norm`` = ``torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm)`` in front of the update, without a pass that rewrites the
     gradients: one read of the active gradient arena leaves partial sums of squares in scratch allocated HERE, once (so a captured graph reuses
     it), and the AdamW kernel scales the gradients by the clip coefficient on their way in.  A shard clips by the norm of the WHOLE arena.
-    ``grad_norm`` (device scalar, no host sync) holds the pre-clip norm of the gradients x ``grad_scale`` after every clipped step."""
+    ``grad_norm`` (device scalar, no host sync) holds the pre-clip norm of the gradients x ``grad_scale`` after every clipped step.
 
-    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, shard=None, max_grad_norm=None):
+    ``groups`` = torch.optim.AdamW's param_groups: a list of ``{lr_mult: 1.0, weight_decay: <the default>, frozen: False}``; group i updates the
+    arena tiles ``arena.tile_group`` assigns to it (ParamArena(group_of=...)) with lr x lr_mult and its own weight decay, a frozen group's tiles
+    are skipped unread and left out of the clipping norm.  The table lives on the device: ``set_group`` changes lr_mult / weight_decay between
+    replays of a captured graph without recapture, as ``set_lr`` does for the learning rate; membership and ``frozen`` are fixed here.  Not
+    available under the fp16 dynamic loss scale (NotImplementedError).  Frozen PARAMETERS need no group: the arena keeps them out of range."""
+
+    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, shard=None, max_grad_norm=None, groups=None):
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError("max_grad_norm must be positive (got %r); None = no clipping" % (max_grad_norm,))
+        self.group_table = None
+        if groups:
+            if arena.tile_group is None:
+                raise ValueError("FlatAdamW(groups=...) needs an arena laid out for groups: ParamArena(model, cuts, group_of={name: group id})")
+            if not 1 <= len(groups) <= 255 or int(arena.tile_group.max()) >= len(groups):
+                raise ValueError("%d groups for tile ids up to %d (1..255 groups, every id below the count)" % (len(groups), int(arena.tile_group.max())))
+            bad = [k for g in groups for k in g if k not in ("lr_mult", "weight_decay", "frozen")]
+            if bad:
+                raise ValueError("unknown group keys %s (lr_mult, weight_decay, frozen)" % sorted(set(bad)))
+            rows = [[float(g.get("lr_mult", 1.0)), float(g.get("weight_decay", weight_decay)), 1.0 if g.get("frozen", False) else 0.0] for g in groups]
+            self.group_table = torch.tensor(rows, dtype=torch.float32, device=arena.params.device)
         self.arena = arena
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
@@ -191,12 +227,35 @@ class FlatAdamW:
     def set_lr(self, lr):
         self.state[1] = lr   # train.py:194-199 (x0.1 at epochs 30 / 40)
 
+    def set_group(self, i, lr_mult=None, weight_decay=None):
+        """Writes group i's row of the device table in place (a captured graph reads it at replay)."""
+        if self.group_table is None or not 0 <= i < self.group_table.shape[0]:
+            raise ValueError("no parameter group %r" % (i,))
+        if lr_mult is not None:
+            self.group_table[i, 0] = float(lr_mult)
+        if weight_decay is not None:
+            self.group_table[i, 1] = float(weight_decay)
+
     def zero_grad(self, set_to_none=False):
         self.arena.zero_grad()
+
+    def _step_groups(self, gs):
+        a, tiles = self.arena, self.arena.tile_group
+        if self.hi == self.lo:      # an empty ZeRO-1 shard: only the step counter moves
+            self.state[0] += 1
+            return
+        clip = {}
+        if self.max_grad_norm is not None:      # the norm of the WHOLE active arena without the frozen groups' tiles
+            ops.grad_sumsq_groups(a.grads[:a.active_numel], tiles, self.group_table, self._sumsq_parts)
+            clip = dict(partials=self._sumsq_parts, n_norm=a.active_numel, max_norm=self.max_grad_norm, norm_out=self.grad_norm)
+        ops.adamw_groups_(a.params[self.lo:self.hi], a.grads[self.lo:self.hi], self.exp_avg, self.exp_avg_sq, self.state, tiles[self.lo // _ALIGN:],
+                          self.group_table, self.betas[0], self.betas[1], self.eps, grad_scale=gs, **clip)
 
     def step(self):
         a = self.arena
         ls = getattr(self, "ls_state", None)
+        if ls is not None and self.group_table is not None:
+            raise NotImplementedError("parameter groups under the fp16 dynamic loss scale: tf_adamw_groups_f32 has no dynamic-scale form (use a static loss_scale)")
         if ls is not None and self.max_grad_norm is None:      # fp16 mode with the dynamic loss scale: overflow check over the WHOLE (reduced) gradient arena, skip-or-update, scale update
             ops.adamw_dynscale_(a.params[self.lo:self.hi], a.grads[self.lo:self.hi], self.exp_avg, self.exp_avg_sq, self.state, ls, a.grads[:a.active_numel],
                                 self.betas[0], self.betas[1], self.eps, self.weight_decay)
@@ -209,6 +268,8 @@ class FlatAdamW:
             red = getattr(self, "reducer", None)
             if red is not None:      # defer_scale: the arena holds the all-reduced SUM, the mean's 1 / world rides on the gradient scale (GradReducer.grad_scale)
                 gs = gs * red.grad_scale()
+        if self.group_table is not None:
+            return self._step_groups(gs)
         if self.max_grad_norm is not None:
             g_all = a.grads[:a.active_numel]
             ops.grad_sumsq(g_all, self._sumsq_parts)
@@ -243,15 +304,22 @@ class FlatAdamW:
         sd = dict(exp_avg=ea, exp_avg_sq=es, state=self.state, active_numel=self.arena.active_numel, layout=self._layout())
         if getattr(self, "ls_state", None) is not None:      # fp16 mode: {scale, clean steps, found_inf, growth interval} - a resumed run continues the scale schedule
             sd["ls_state"] = self.ls_state
+        if self.group_table is not None:      # the table as it stands (set_group included) and every updated parameter's group
+            sd["groups"] = [dict(lr_mult=r[0], weight_decay=r[1], frozen=bool(r[2])) for r in self.group_table.tolist()]
+            tiles = self.arena.tile_group.tolist()
+            sd["param_group"] = {name: tiles[off // _ALIGN] for name, off, _ in self._layout()}
         return sd
 
     def load_state_dict(self, sd):
         """Accepts the full state written by ``state_dict`` on any world size / with any backward cuts: the moments are copied parameter
         by parameter (matched by name); a sharded optimizer keeps its own slice.  A state without a layout (written before the layout
         was recorded) is only accepted when this arena has no cuts - its order is then the one those files were written in on one GPU;
-        anything else raises instead of silently assigning moments to the wrong parameters."""
+        anything else raises instead of silently assigning moments to the wrong parameters.  A state written without groups loads into an
+        optimizer with groups (the moments do not depend on them); with the same number of groups the saved lr_mult / weight_decay values are
+        put back.  Moments of parameters that are frozen NOW (behind ``active_numel``) are ignored."""
         n = self.arena.active_numel
         mine = self._layout()
+        inactive = {name for name, p, off in self.arena.layout if off >= n}
         theirs = sd.get("layout")
         if theirs is None:
             if len(self.arena.segment_ranges) > 1:
@@ -263,8 +331,9 @@ class FlatAdamW:
         if not same:
             a, b = {t[0]: t for t in theirs}, {t[0]: t for t in mine}
             missing = [k for k in b if k not in a or a[k][2] != b[k][2]]
-            if missing or len(a) != len(b):
-                raise ValueError("optimizer state does not match this model: %d parameters differ (e.g. %s)" % (max(len(missing), abs(len(a) - len(b))), missing[:3]))
+            extra = [k for k in a if k not in b and k not in inactive]
+            if missing or extra:
+                raise ValueError("optimizer state does not match this model: %d parameters differ (e.g. %s)" % (len(missing) + len(extra), (missing + extra)[:3]))
         for name, dst in (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
             src = sd[name].to(dst.device)
             if src.numel() != sd.get("active_numel", n):
@@ -280,6 +349,8 @@ class FlatAdamW:
                 raise ValueError("optimizer state %s has %d elements, expected %d" % (name, full.numel(), n))
             dst.copy_(full[self.lo:self.hi] if dst.numel() != n else full)
         self.state.copy_(sd["state"])
+        if self.group_table is not None and len(sd.get("groups") or ()) == self.group_table.shape[0]:
+            self.group_table[:, :2] = torch.tensor([[g["lr_mult"], g["weight_decay"]] for g in sd["groups"]], dtype=torch.float32, device=self.group_table.device)
         if sd.get("ls_state") is not None and getattr(self, "ls_state", None) is not None:
             self.ls_state.copy_(sd["ls_state"].to(self.ls_state.device))      # in place: the Engine's backward seed is a view of this tensor
 
@@ -414,7 +485,7 @@ class Engine:
 
     def __init__(self, model, config, lr=1e-4, use_graph=False, group=None, bucket_mb=64.0, wp_only=False, autotune=True, plan_file=None,
                  zero_redundancy_optimizer=False, sync_batch_norm=False, cuts=None, precision=None, grad_dtype="fp32", loss_scale=None, deterministic=None,
-                 accumulate=1, max_grad_norm=None):
+                 accumulate=1, max_grad_norm=None, param_groups=None, freeze=None, freeze_bn=True):
         """``cuts``: points (cut_key: int c = after fusion stage c; (i, 0, 0) = between the stage-i trunks and GPT i; (i, 1, j) = inside GPT i
         in front of Block j) at which the backward is cut into separately enqueued (and separately captured) segments whose gradient
         ranges are all-reduced while the next segment runs.  None = DEFAULT_CUTS when there is more than one rank (and the backbone is a
@@ -438,7 +509,42 @@ class Engine:
         saves rank 0's buffers only), and each micro-batch draws its dropout masks from the seed that advances per call (ranks seed
         independently).  Under the fp16 dynamic loss scale the scale is constant inside a window and an overflow skips the window's update.
         ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_`` of the (mean) gradients in front of AdamW (FlatAdamW); ``optimizer.grad_norm`` is
-        the pre-clip norm as a device scalar.  Both off by default: same launches, same captured graph, same bits."""
+        the pre-clip norm as a device scalar.  Both off by default: same launches, same captured graph, same bits.
+        Fine-tuning (all off by default: same launches, same graph, same bits).  ``freeze``: parameter-name prefixes whose parameters get
+        ``requires_grad = False``; every parameter that does not require a gradient at construction is FROZEN: never updated, never decayed, no
+        moments, outside the clipping norm (torch.optim.AdamW / clip_grad_norm_ semantics for grad-None parameters), in every precision and mode -
+        the arena files them behind ``active_numel``.  Their weight-gradient kernels still run where the backward passes through.
+        ``param_groups``: a list of ``{"match": prefix or list of prefixes | "match_1d": True, "lr_mult": 1.0, "weight_decay": <AdamW's 0.01>}``; a
+        parameter joins the FIRST entry it matches (``match_1d``: every parameter with ndim <= 1 - norm weights and biases; pos_emb has 3
+        dimensions), the rest form the default group 0.  ``optimizer.set_group(i + 1, ...)`` changes entry i's values later, also between replays of
+        a captured graph.  An unknown prefix raises ValueError, [] is None; under the fp16 dynamic loss scale groups raise NotImplementedError.
+        ``freeze_bn``: every BatchNorm whose weight and bias are both frozen is put in eval() - running statistics fixed, normalisation and the
+        backward through it take the frozen-statistics form - and ``apply_frozen_modes()`` puts it back there after a ``model.train()``."""
+        names = [n for n, _ in model.named_parameters()]
+        prefixes = lambda m: [m] if isinstance(m, str) else list(m)
+
+        def matched(prefix):
+            hit = [n for n in names if n.startswith(prefix)]
+            if not hit:
+                raise ValueError("no parameter name starts with %r" % (prefix,))
+            return hit
+        for prefix in prefixes(freeze or ()):
+            hit = set(matched(prefix))
+            for n, p in model.named_parameters():
+                if n in hit:
+                    p.requires_grad_(False)
+        group_of, groups = None, None
+        if param_groups:
+            group_of, groups = {n: 0 for n in names}, [{}]
+            for i, entry in enumerate(param_groups):
+                bad = [k for k in entry if k not in ("match", "match_1d", "lr_mult", "weight_decay")]
+                if bad or ("match" in entry) == bool(entry.get("match_1d")):
+                    raise ValueError("param_groups[%d]: needs either 'match' or 'match_1d': True, plus lr_mult / weight_decay (got %r)" % (i, entry))
+                hit = {n for n, p in model.named_parameters() if p.dim() <= 1} if entry.get("match_1d") else {n for pre in prefixes(entry["match"]) for n in matched(pre)}
+                for n in hit:
+                    if group_of[n] == 0:      # first match wins
+                        group_of[n] = i + 1
+                groups.append({k: entry[k] for k in ("lr_mult", "weight_decay") if k in entry})
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError("accumulate must be an integer >= 1 (got %r)" % (accumulate,))
         if max_grad_norm is not None and not max_grad_norm > 0:
@@ -475,14 +581,20 @@ class Engine:
         self.cuts = tuple(k for k in keys if not (k[1] == 1 and k[2] >= nblk))       # a cut in front of a Block the model does not have is dropped
         if can_cut:
             backbone._cuts = frozenset(self.cuts)
-        self.arena = ParamArena(model, self.cuts)
+        self.arena = ParamArena(model, self.cuts, group_of)
+        live = lambda p: p is not None and p.requires_grad
+        self._frozen_bn = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.weight is not None
+                           and not live(m.weight) and not live(m.bias)] if freeze_bn else []
+        self.apply_frozen_modes()
         self.reducer = GradReducer(self.arena, group, bucket_mb, grad_dtype)
         self.zero = bool(zero_redundancy_optimizer) and self.reducer.world > 1      # train.py:143-146
         rank = dist.get_rank(group) if self.zero else 0
         dynamic_ls = loss_scale is None and ops.get_precision() == "fp16"
         if max_grad_norm is None and dynamic_ls and self.accumulate > 1:
             max_grad_norm = float("inf")      # tf_adamw_dynscale_f32 has no gradient scale next to the device-side one: the window's 1 / k rides on the clipping entry, which never clips here
-        self.optimizer = FlatAdamW(self.arena, lr=lr, shard=(rank, self.reducer.world) if self.zero else None, max_grad_norm=max_grad_norm)
+        if dynamic_ls and groups:
+            raise NotImplementedError("param_groups under the fp16 dynamic loss scale (tf_adamw_groups_f32 has no dynamic-scale form): pass a static loss_scale")
+        self.optimizer = FlatAdamW(self.arena, lr=lr, shard=(rank, self.reducer.world) if self.zero else None, max_grad_norm=max_grad_norm, groups=groups)
         self.optimizer.accum_scale = 1.0 / self.accumulate
         self.ls_state = None
         if dynamic_ls:
@@ -512,6 +624,12 @@ class Engine:
         self._graphs = None
         self._static = None
         self._out = None
+
+    def apply_frozen_modes(self):
+        """Puts every BatchNorm whose weight and bias are frozen (``freeze_bn``) in eval(): call it after anything that switched the model to
+        train() (``Trainer.train`` and ``Trainer.validate`` do)."""
+        for m in self._frozen_bn:
+            m.eval()
 
     def load_data_compute_loss(self, data):
         """train.py:246-293 (transFuser branch); ``data`` tensors must already be on the device."""
@@ -773,6 +891,7 @@ class Trainer:
 
     def train(self):
         self.eng.model.train()
+        self.eng.apply_frozen_modes()      # model.train() also switched the frozen BatchNorms: back to eval()
         num_batches, loss_epoch = 0, torch.zeros((), device=self.device)
         detailed = {k: torch.zeros((), device=self.device) for k in self.detailed_losses}
         for data in self.dataloader_train:
@@ -801,6 +920,7 @@ class Trainer:
             num_batches += 1
         self.log_losses(loss_epoch, detailed, max(num_batches, 1), 'val_')
         self.eng.model.train()
+        self.eng.apply_frozen_modes()
 
     def log_losses(self, loss_epoch, detailed_losses_epoch, num_batches, prefix='', extra=None):
         """``extra``: scalars of this rank logged as they are (not averaged over batches or ranks), e.g. grad_norm."""
@@ -871,10 +991,26 @@ def build_parser():
     p.add_argument('--deterministic', type=int, default=0, help='1: bitwise-reproducible fp32 train step on one GPU (fixed-order reductions instead of fp32 atomics; Engine(deterministic=True))')
     p.add_argument('--accumulate', type=int, default=1, help='micro-batches per AdamW update: batch_size * accumulate on one GPU is the effective batch of that many data-parallel ranks (Engine(accumulate=k))')
     p.add_argument('--max_grad_norm', type=float, default=0.0, help='clip the global gradient norm in front of AdamW (torch.nn.utils.clip_grad_norm_); 0 = off')
+    p.add_argument('--freeze', type=str, nargs='*', default=[], metavar='PREFIX', help='fine-tuning: parameter-name prefixes that are not trained (Engine(freeze=...)); their BatchNorms keep their running statistics')
+    p.add_argument('--lr_mult', type=str, nargs='*', default=[], metavar='PREFIX=MULT', help='learning-rate multiplier of the parameters under a prefix, e.g. _model.image_encoder=0.1 (one AdamW group per entry, first match wins)')
+    p.add_argument('--no_decay_1d', type=int, default=0, help='1: weight decay 0 for norm weights and biases (ndim <= 1) that no --lr_mult prefix claimed')
     p.add_argument('--height', type=int, default=160, help="RGB height of the synthetic samples (the dataset's crop is 160 x 704)")
     p.add_argument('--num_workers', type=int, default=None)
     p.add_argument('--width', type=int, default=704)
     return p
+
+
+def cli_param_groups(args):
+    """--lr_mult PREFIX=MULT ... and --no_decay_1d as Engine ``param_groups`` (the lr_mult entries first: first match wins)."""
+    out = []
+    for item in args.lr_mult:
+        prefix, sep, mult = item.rpartition("=")
+        if not sep or not prefix:
+            raise ValueError("--lr_mult takes PREFIX=MULT (got %r)" % item)
+        out.append({"match": prefix, "lr_mult": float(mult)})
+    if args.no_decay_1d:
+        out.append({"match_1d": True, "weight_decay": 0.0})
+    return out
 
 
 def main(argv=None):
@@ -911,7 +1047,7 @@ def main(argv=None):
     eng = Engine(model, config, lr=args.lr, use_graph=bool(args.use_graph) and cuda, wp_only=bool(args.wp_only),
                  zero_redundancy_optimizer=bool(args.zero_redundancy_optimizer), sync_batch_norm=bool(args.sync_batch_norm), precision=args.precision if cuda else None,
                  deterministic=True if (args.deterministic and cuda) else None, accumulate=args.accumulate,
-                 max_grad_norm=args.max_grad_norm if args.max_grad_norm != 0 else None)
+                 max_grad_norm=args.max_grad_norm if args.max_grad_norm != 0 else None, param_groups=cli_param_groups(args), freeze=args.freeze)
     if args.load_file is not None and os.path.exists(args.load_file.replace("model_", "optimizer_")):
         eng.optimizer.load_state_dict(torch.load(args.load_file.replace("model_", "optimizer_"), map_location=device))
     shared_dict = None
