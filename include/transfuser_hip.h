@@ -535,6 +535,27 @@ int tf_grad_sumsq_groups_f32(const float* g, int64_t n, const uint8_t* tile_grou
 int tf_adamw_groups_f32(float* p, const float* g, float* m, float* v, int64_t n, float* state_dev, float beta1, float beta2, float eps, float grad_scale,
                         const uint8_t* tile_group, const float* table, int ngroups, const float* partials, int nparts, int64_t n_norm, float max_norm,
                         float* norm_out, void* stream);
+/* Exponential moving average of the weights (timm's ModelEmaV2, with ModelEmaV3's optional warm-up; the reference keeps none - this sits beside
+ * its optimizer and checkpoint code, train.py:142,204-210,381-384).  A pass of its own BEHIND the optimizer step, 12 B per parameter (p read,
+ * e read, e written); the AdamW kernels are not involved.  Element-wise throughout: no atomics, no workspace, nothing allocated, capturable,
+ * legal under tf_set_deterministic(1).
+ * ema_state = {decay, num_updates, last_opt_step, coef} floats on the device, so a replayed graph advances it without the host.
+ * tf_ema_tick_f32 (one thread; a launch of its own in front of the apply launches, which only read the state): with t = opt_state[0]
+ * (FlatAdamW's {step, lr}) the step is a no-op, coef = 0, when t == last_opt_step - the optimizer skipped an overflowed fp16 step and did not
+ * count it - or when t % every != 0; otherwise n = num_updates, d = warmup ? min(decay, (1 + n) / (10 + n)) : decay, coef = 1 - d,
+ * num_updates = n + 1, last_opt_step = t.  opt_state NULL: every call updates (last_opt_step stays).  every >= 1.
+ * tf_ema_apply_f32: e = fma(coef, p - e, e) over n floats, n % 4 == 0, both ranges 16-byte aligned and disjoint; returns at once when coef == 0.
+ * tf_ema_apply_multi_f32: the same over a device table of (ema, live, count) entries of any alignment and count >= 1, one launch (the module
+ * buffers outside the arena: BatchNorm running_mean / running_var), nentries >= 1.
+ * tf_swap_f32 / tf_swap_multi_f32 exchange the contents of a / b (n % 4 == 0, 16-byte aligned) or of every (ema, live) pair of the table, in
+ * place.  tf_swap_f32 refuses overlapping ranges; the ranges of a table live on the device and must be pairwise disjoint - ops.ema_table
+ * refuses to build a table whose ranges overlap.  A refused call launches nothing. */
+typedef struct { float* ema; float* live; int64_t count; } tf_ema_item;
+int tf_ema_tick_f32(float* ema_state, const float* opt_state, int every, int warmup, void* stream);
+int tf_ema_apply_f32(float* ema, const float* p, int64_t n, const float* ema_state, void* stream);
+int tf_ema_apply_multi_f32(const tf_ema_item* table_dev, int nentries, const float* ema_state, void* stream);
+int tf_swap_f32(float* a, float* b, int64_t n, void* stream);
+int tf_swap_multi_f32(const tf_ema_item* table_dev, int nentries, void* stream);
 /* lidar_to_histogram_features (data.py:446-470): points (B, max_points, stride>=3) f32 -> (B,2,256,256),
  * integer-exact; num_points may be NULL. */
 int tf_lidar_hist_f32(const float* points, const int32_t* num_points, int B, int max_points, int point_stride, float* out, void* stream);

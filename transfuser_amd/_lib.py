@@ -37,6 +37,10 @@ class ConvGeom(ctypes.Structure):
     _fields_ = [(n, c_i) for n in ("B", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "ksize", "stride", "pad", "groups")]
 
 
+class EmaItem(ctypes.Structure):      # include/transfuser_hip.h: tf_ema_item
+    _fields_ = [("ema", c_p), ("live", c_p), ("count", c_l)]
+
+
 def _declare(lib):
     lib.tf_last_error.restype = ctypes.c_char_p
     lib.tf_version.restype = c_i

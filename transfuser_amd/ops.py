@@ -1635,6 +1635,78 @@ def adamw_groups_(p, g, m, v, state, tile_group, table, beta1=0.9, beta2=0.999, 
     _hbm_end(_h, "adamw (28 B / parameter: p, g, m, v read; p, m, v written)", 28 * n)
 
 
+# ---- weight EMA (csrc/ema.cpp): ema_state = [decay, num_updates, last_opt_step, coef] floats on the device; the tick decides, the applies read
+def ema_tick_(ema_state, opt_state=None, every=1, warmup=False):
+    """Decides on the device whether this step updates the average: ``opt_state`` = FlatAdamW's [step, lr]; a step the optimizer did not count
+    (fp16 overflow) or one with step % every != 0 leaves coef = 0, otherwise coef = 1 - decay (``warmup``: 1 - min(decay, (1 + n) / (10 + n)))
+    and num_updates advances.  Without ``opt_state`` every call updates."""
+    assert ema_state.dtype == torch.float32 and ema_state.numel() == 4 and ema_state.is_contiguous(), "ema_state = 4 contiguous floats"
+    assert opt_state is None or (opt_state.dtype == torch.float32 and opt_state.numel() >= 1 and opt_state.device == ema_state.device)
+    check(L().tf_ema_tick_f32(ptr(ema_state), ptr(opt_state), int(every), int(bool(warmup)), stream_of(ema_state)), "tf_ema_tick_f32")
+
+
+def ema_apply_(ema, p, ema_state):
+    """ema += coef * (p - ema) over a flat fp32 range (numel % 4 == 0, 16-byte aligned, disjoint); nothing is touched when the tick left coef = 0.
+    The HBM census books the 12 B / parameter of an updating call for every call: coef lives on the device, so a call that returns at once
+    (an ``every`` > 1 off-step, a skipped fp16 step) is over-counted there - divide by ``every`` when reading it."""
+    assert ema.dtype == p.dtype == torch.float32 and ema.is_contiguous() and p.is_contiguous() and ema.numel() == p.numel(), (ema.shape, p.shape)
+    _h = _hbm_begin()
+    check(L().tf_ema_apply_f32(ptr(ema), ptr(p), ctypes.c_int64(ema.numel()), ptr(ema_state), stream_of(ema)), "tf_ema_apply_f32")
+    _hbm_end(_h, "ema (12 B / parameter when the step updates: p, e read; e written)", 12 * ema.numel())
+
+
+def ema_table(pairs):
+    """Device table of (ema, live, count) entries for ``ema_apply_multi_`` / ``swap_multi_`` from pairs of equally sized contiguous fp32 tensors
+    of any alignment -> (table bytes on the device, entries, floats).  The caller owns it and keeps the tensors alive.  The C entries cannot
+    read a device table, so overlapping ranges are refused HERE (ValueError): every range, ema or live, must be disjoint from every other.
+    Built outside graph capture."""
+    pairs = list(pairs)
+    if not pairs:
+        raise ValueError("ema_table: at least one (ema, live) pair")
+    items = (_lib.EmaItem * len(pairs))()
+    spans, total = [], 0
+    for it, (e, p) in zip(items, pairs):
+        if not (e.dtype == p.dtype == torch.float32 and e.is_contiguous() and p.is_contiguous() and e.numel() == p.numel() >= 1 and e.device == p.device):
+            raise ValueError("ema_table: every pair must be two contiguous fp32 tensors of the same size >= 1 on one device (got %s %s, %s %s)"
+                             % (e.dtype, tuple(e.shape), p.dtype, tuple(p.shape)))
+        it.ema, it.live, it.count = e.data_ptr(), p.data_ptr(), e.numel()
+        spans += [(e.data_ptr(), e.data_ptr() + 4 * e.numel()), (p.data_ptr(), p.data_ptr() + 4 * p.numel())]
+        total += e.numel()
+    spans.sort()
+    for (_, hi), (lo, _) in zip(spans, spans[1:]):
+        if lo < hi:
+            raise ValueError("ema_table: two ranges of the table overlap")
+    dev = pairs[0][0].device
+    assert not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()), "the EMA table must exist before graph capture"
+    tab = torch.empty(ctypes.sizeof(items), dtype=torch.uint8, device=dev)
+    tab.copy_(torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8))
+    return tab, len(pairs), total
+
+
+def ema_apply_multi_(table, ema_state):
+    """``ema_apply_`` over every entry of an ``ema_table`` in one launch (the module buffers outside the arena)."""
+    tab, n, total = table
+    _h = _hbm_begin()
+    check(L().tf_ema_apply_multi_f32(ptr(tab), int(n), ptr(ema_state), stream_of(tab)), "tf_ema_apply_multi_f32")
+    _hbm_end(_h, "ema (12 B / parameter when the step updates: p, e read; e written)", 12 * total)
+
+
+def swap_(a, b):
+    """Exchanges the contents of two flat fp32 ranges in place (numel % 4 == 0, 16-byte aligned, not overlapping)."""
+    assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel(), (a.shape, b.shape)
+    _h = _hbm_begin()
+    check(L().tf_swap_f32(ptr(a), ptr(b), ctypes.c_int64(a.numel()), stream_of(a)), "tf_swap_f32")
+    _hbm_end(_h, "swap (16 B / parameter: a, b read; a, b written)", 16 * a.numel())
+
+
+def swap_multi_(table):
+    """Exchanges the two tensors of every entry of an ``ema_table`` in one launch."""
+    tab, n, total = table
+    _h = _hbm_begin()
+    check(L().tf_swap_multi_f32(ptr(tab), int(n), stream_of(tab)), "tf_swap_multi_f32")
+    _hbm_end(_h, "swap (16 B / parameter: a, b read; a, b written)", 16 * total)
+
+
 def cast_bf16(x, out=None):
     """fp32 -> bf16 (round to nearest even)."""
     if out is None:

@@ -485,7 +485,7 @@ class Engine:
 
     def __init__(self, model, config, lr=1e-4, use_graph=False, group=None, bucket_mb=64.0, wp_only=False, autotune=True, plan_file=None,
                  zero_redundancy_optimizer=False, sync_batch_norm=False, cuts=None, precision=None, grad_dtype="fp32", loss_scale=None, deterministic=None,
-                 accumulate=1, max_grad_norm=None, param_groups=None, freeze=None, freeze_bn=True):
+                 accumulate=1, max_grad_norm=None, param_groups=None, freeze=None, freeze_bn=True, ema_decay=None, ema_every=1, ema_warmup=False):
         """``cuts``: points (cut_key: int c = after fusion stage c; (i, 0, 0) = between the stage-i trunks and GPT i; (i, 1, j) = inside GPT i
         in front of Block j) at which the backward is cut into separately enqueued (and separately captured) segments whose gradient
         ranges are all-reduced while the next segment runs.  None = DEFAULT_CUTS when there is more than one rank (and the backbone is a
@@ -519,7 +519,17 @@ class Engine:
         dimensions), the rest form the default group 0.  ``optimizer.set_group(i + 1, ...)`` changes entry i's values later, also between replays of
         a captured graph.  An unknown prefix raises ValueError, [] is None; under the fp16 dynamic loss scale groups raise NotImplementedError.
         ``freeze_bn``: every BatchNorm whose weight and bias are both frozen is put in eval() - running statistics fixed, normalisation and the
-        backward through it take the frozen-statistics form - and ``apply_frozen_modes()`` puts it back there after a ``model.train()``."""
+        backward through it take the frozen-statistics form - and ``apply_frozen_modes()`` puts it back there after a ``model.train()``.
+        ``ema_decay`` = d in (0, 1): ``self.ema`` (ema.WeightEMA, None when off) keeps an exponential moving average of the active arena range and
+        of every floating-point module buffer, e += (1 - d) (p - e), as three launches behind the optimizer step and the weight-copy refresh -
+        inside the captured optimizer graph / the fused single graph; with ZeRO-1 behind the parameter all-gather, eagerly, every rank averaging
+        the whole range.  An accumulation window updates once, an overflow-skipped fp16 step not at all.  ``ema_every`` = k: only optimizer steps
+        k, 2k, ... update; ``ema_warmup``: d_t = min(d, (1 + n) / (10 + n)) with n the updates so far.  ``with engine.ema_weights():`` computes
+        with the averaged values.  Off by default: same launches, same captured graph, same bits."""
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must lie in (0, 1) (got %r); None = no average" % (ema_decay,))
+        if int(ema_every) != ema_every or ema_every < 1:
+            raise ValueError("ema_every must be an integer >= 1 (got %r)" % (ema_every,))
         names = [n for n, _ in model.named_parameters()]
         prefixes = lambda m: [m] if isinstance(m, str) else list(m)
 
@@ -624,6 +634,17 @@ class Engine:
         self._graphs = None
         self._static = None
         self._out = None
+        self.ema = None
+        if ema_decay is not None:      # last: a copy of the (broadcast) parameters and buffers as they stand now
+            from .ema import WeightEMA
+            self.ema = WeightEMA(model, self.arena, self.optimizer, ema_decay, ema_every, ema_warmup)
+
+    def ema_weights(self):
+        """``with engine.ema_weights():`` the model's parameters and float buffers hold the averaged values (swapped in place, swapped back on
+        the way out, also on an exception).  Does not nest; not while a stream is capturing; no ``train_step`` inside."""
+        if self.ema is None:
+            raise RuntimeError("Engine.ema_weights(): no average is kept (construct the Engine with ema_decay=...)")
+        return self.ema.weights()
 
     def apply_frozen_modes(self):
         """Puts every BatchNorm whose weight and bias are frozen (``freeze_bn``) in eval(): call it after anything that switched the model to
@@ -662,6 +683,8 @@ class Engine:
         self.optimizer.step()
         if ops.lowp_storage() and not self.zero:
             ops.lowp_refresh_weights()
+        if self.ema is not None and not self.zero:
+            self.ema.update()
 
     def _after_opt(self):
         """Eager tail of a step behind AdamW (outside the captured graphs: the all-gather is an RCCL call)."""
@@ -669,6 +692,8 @@ class Engine:
             self.reducer.all_gather_params(self.optimizer)
             if ops.lowp_storage():
                 ops.lowp_refresh_weights()
+            if self.ema is not None:      # every rank averages the whole gathered range: redundant, but the ranks stay identical and a swap needs no collective
+                self.ema.update()
 
     def _piece0_impl(self, data):
         if self.accumulate == 1:      # a window of k > 1 micro-batches is zeroed once, by _begin_micro, outside the (captured) piece
@@ -758,6 +783,8 @@ class Engine:
     def train_step(self, data):
         """One micro-batch: returns (total loss, dict of the 11 detailed losses) as device tensors (no host sync).  With ``accumulate`` = k
         every k-th call also updates the parameters."""
+        if self.ema is not None and self.ema.swapped:
+            raise RuntimeError("train_step inside ema_weights(): the live weights are swapped out")
         if not self.use_graph:
             return self._eager_step(data)
         if self._graphs is None:
@@ -786,7 +813,8 @@ class Engine:
         # the eager loop / the reference's one-update-per-batch loop (train.py:304-316).  Everything a step mutates is snapshotted and put
         # back: parameters, AdamW moments + step counter, BatchNorm running statistics / dropout seed (all module buffers).
         opt = self.optimizer
-        snap = [(t, t.clone()) for t in [self.arena.params, opt.exp_avg, opt.exp_avg_sq, opt.state] + ([self.ls_state] if self.ls_state is not None else []) + list(self.model.buffers())]
+        snap = [(t, t.clone()) for t in [self.arena.params, opt.exp_avg, opt.exp_avg_sq, opt.state] + ([self.ls_state] if self.ls_state is not None else []) + list(self.model.buffers())
+                                      + (self.ema.tensors() if self.ema is not None else [])]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):   # warm-up on a side stream (allocator + lazy inits) before capture
@@ -836,7 +864,33 @@ class Engine:
         osd = self.optimizer.state_dict(self.reducer.group)
         if self.reducer.world == 1 or dist.get_rank(self.reducer.group) == 0:
             torch.save(self.model.state_dict(), "%s/model_%d.pth" % (path_prefix, epoch))
+            osd = self._save_ema(osd, "%s/model_ema_%d.pth" % (path_prefix, epoch))
             torch.save({k: (v.cpu() if torch.is_tensor(v) else v) for k, v in osd.items()}, "%s/optimizer_%d.pth" % (path_prefix, epoch))
+
+    def _save_ema(self, osd, path, prefix=""):
+        """With an average: writes ``model.state_dict()`` taken inside ``ema_weights()`` to ``path`` (the reference's key names, so
+        ``load_reference_checkpoint`` and the reference agent, submission_agent.py:94-96, load it like model_<epoch>.pth) and returns the optimizer
+        state with the average's counters under "ema" (FlatAdamW.load_state_dict reads named keys only)."""
+        if self.ema is None:
+            return osd
+        if self.arena.params.is_cuda:
+            torch.cuda.current_stream().synchronize()
+        with self.ema_weights():
+            torch.save({prefix + k: v for k, v in self.model.state_dict().items()}, path)
+        st = self.ema.state.tolist()
+        return dict(osd, ema=dict(num_updates=int(st[1]), last_opt_step=int(st[2]), decay=self.ema.decay))
+
+    def load_ema(self, model_ema_path, optimizer_path=None, map_location=None):
+        """Resume: the average from a saved model_ema_<epoch>.pth and its counters from the "ema" entry of optimizer_<epoch>.pth -> True;
+        False (the average stays the copy of the loaded weights made at construction) when the file is missing."""
+        if self.ema is None or not os.path.exists(model_ema_path):
+            return False
+        self.ema.load_model_state_dict(torch.load(model_ema_path, map_location=map_location))
+        if optimizer_path is not None and os.path.exists(optimizer_path):
+            counters = torch.load(optimizer_path, map_location="cpu").get("ema")
+            if counters is not None:
+                self.ema.load_counters(counters)
+        return True
 
 
 # ================================================================================================ command line (train.py:27-211, 295-384)
@@ -906,9 +960,7 @@ class Trainer:
         self.log_losses(float(loss_epoch), {k: float(v) for k, v in detailed.items()}, max(num_batches, 1), '', extra)
         self.cur_epoch += 1
 
-    @torch.inference_mode()
-    def validate(self):
-        self.eng.model.eval()
+    def _validate_pass(self, prefix):
         num_batches, loss_epoch = 0, 0.0
         detailed = {k: 0.0 for k in self.detailed_losses}
         for data in self.dataloader_val:
@@ -918,7 +970,18 @@ class Trainer:
                 detailed[k] += val
                 loss_epoch += val
             num_batches += 1
-        self.log_losses(loss_epoch, detailed, max(num_batches, 1), 'val_')
+        self.log_losses(loss_epoch, detailed, max(num_batches, 1), prefix)
+
+    @torch.inference_mode()
+    def validate(self):
+        """``val_*`` from the live weights; with an average (``--ema_validate`` both | ema | live) also ``val_ema_*`` from the averaged ones."""
+        self.eng.model.eval()
+        mode = getattr(self.args, "ema_validate", "both") if getattr(self.eng, "ema", None) is not None else "live"
+        if mode != "ema":
+            self._validate_pass('val_')
+        if mode != "live":
+            with self.eng.ema_weights():
+                self._validate_pass('val_ema_')
         self.eng.model.train()
         self.eng.apply_frozen_modes()
 
@@ -953,6 +1016,7 @@ class Trainer:
             if self.parallel:   # the reference saves the DDP-wrapped module: keys carry 'module.' (submission_agent.py:94-96 strips it)
                 sd = {"module." + k: v for k, v in sd.items()}
             torch.save(sd, os.path.join(self.args.logdir, 'model_%d.pth' % self.cur_epoch))
+            osd = self.eng._save_ema(osd, os.path.join(self.args.logdir, 'model_ema_%d.pth' % self.cur_epoch), "module." if self.parallel else "")
             torch.save({k: (v.cpu() if torch.is_tensor(v) else v) for k, v in osd.items()}, os.path.join(self.args.logdir, 'optimizer_%d.pth' % self.cur_epoch))
 
 
@@ -994,6 +1058,10 @@ def build_parser():
     p.add_argument('--freeze', type=str, nargs='*', default=[], metavar='PREFIX', help='fine-tuning: parameter-name prefixes that are not trained (Engine(freeze=...)); their BatchNorms keep their running statistics')
     p.add_argument('--lr_mult', type=str, nargs='*', default=[], metavar='PREFIX=MULT', help='learning-rate multiplier of the parameters under a prefix, e.g. _model.image_encoder=0.1 (one AdamW group per entry, first match wins)')
     p.add_argument('--no_decay_1d', type=int, default=0, help='1: weight decay 0 for norm weights and biases (ndim <= 1) that no --lr_mult prefix claimed')
+    p.add_argument('--ema_decay', type=float, default=0.0, help='keep an exponential moving average of the weights with this decay, e.g. 0.9999 (Engine(ema_decay=...)); validated as val_ema_*, saved as model_ema_<epoch>.pth; 0 = off')
+    p.add_argument('--ema_every', type=int, default=1, help='update the average on every k-th optimizer step')
+    p.add_argument('--ema_warmup', type=int, default=0, choices=[0, 1], help='1: decay min(ema_decay, (1 + n) / (10 + n)) over the first updates')
+    p.add_argument('--ema_validate', type=str, default='both', choices=['both', 'ema', 'live'], help='which weights validate() evaluates when an average is kept')
     p.add_argument('--height', type=int, default=160, help="RGB height of the synthetic samples (the dataset's crop is 160 x 704)")
     p.add_argument('--num_workers', type=int, default=None)
     p.add_argument('--width', type=int, default=704)
@@ -1047,9 +1115,14 @@ def main(argv=None):
     eng = Engine(model, config, lr=args.lr, use_graph=bool(args.use_graph) and cuda, wp_only=bool(args.wp_only),
                  zero_redundancy_optimizer=bool(args.zero_redundancy_optimizer), sync_batch_norm=bool(args.sync_batch_norm), precision=args.precision if cuda else None,
                  deterministic=True if (args.deterministic and cuda) else None, accumulate=args.accumulate,
-                 max_grad_norm=args.max_grad_norm if args.max_grad_norm != 0 else None, param_groups=cli_param_groups(args), freeze=args.freeze)
+                 max_grad_norm=args.max_grad_norm if args.max_grad_norm != 0 else None, param_groups=cli_param_groups(args), freeze=args.freeze,
+                 ema_decay=args.ema_decay if args.ema_decay != 0 else None, ema_every=args.ema_every, ema_warmup=bool(args.ema_warmup))
     if args.load_file is not None and os.path.exists(args.load_file.replace("model_", "optimizer_")):
         eng.optimizer.load_state_dict(torch.load(args.load_file.replace("model_", "optimizer_"), map_location=device))
+    if args.load_file is not None and eng.ema is not None:
+        d, f = os.path.split(args.load_file)
+        if not eng.load_ema(os.path.join(d, f.replace("model_", "model_ema_")), os.path.join(d, f.replace("model_", "optimizer_")), map_location=device):
+            print("no %s beside %s: the average starts from the loaded weights" % (f.replace("model_", "model_ema_"), args.load_file))
     shared_dict = None
     if bool(args.use_disk_cache):       # train.py:77-90: decoded samples cached on the fast local storage ($SCRATCH), shared by all ranks
         if str(args.root_dir).startswith("synthetic"):
